@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 r"""Benchmark of the BitBIRCH insertion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-fps M] [--workload fake|ecfp|rdkit]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-fps M] [--workload fake|ecfp|rdkit] [--full]
+                    [--dump-outputs DIR]
 
 N = 1 (BASELINE.json configs[1]): one "step" = `BitBirch.fit` of the whole synthetic workload (1 M synthetic
 2048-bit packed fingerprints, threshold 0.3, branching factor 50, diameter merge) into a fresh HBM-resident
@@ -16,8 +17,13 @@ itself under `python -m torch.distributed.run` with N ranks; when it is set it m
 
 Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (the tree insertion kernel;
 algorithmic bytes = 264 B per inserted element) timed with HIP events on its launch
-stream inside libbbhip; `k1_roofline` is the arr-vec Tanimoto kernel (264 B per row) that the north star's
-HBM target refers to.  `cpu_baseline` is the CPU oracle (a C restatement of the reference path, kind "port").
+stream inside libbbhip during the timed steps.  A plain run does only what that line needs: it sets up, warms
+up, times K steps and prints it.  `--full` adds everything else: the sub-records (end-to-end step, other
+branching factors, workloads, sizes and paths), `k1_roofline` (the arr-vec Tanimoto kernel, 264 B per row,
+that the north star's HBM target refers to) and `k2_valu`, `cpu_baseline` (the CPU oracle, a C restatement
+of the reference path, kind "port") and `regressions` against the previous round's line.
+`--dump-outputs DIR` writes what the last timed step computed (`tree_outputs`) as DIR/<name>.npy; the inputs
+are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -432,7 +438,71 @@ def parse() -> argparse.Namespace:
     ap.add_argument("--dry-run", action="store_true", help="print the plan of the N > 1 job (rows per shard, projected wall time) and exit")
     ap.add_argument("--distributed", action="store_true",
                     help="time the one-rank-per-GPU multiround path even at N=1 (what N>1 always times)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: sub-records, other kernels' rooflines, CPU baselines, the regression "
+                         "record (without it a run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _sample_rows(a, cap: int, seed: int):
+    r"""`a` and None when it has at most `cap` rows, else a fixed seeded sample of `cap` of its rows (in row order) and
+    their row numbers."""
+    import numpy as np
+
+    if a.shape[0] <= cap:
+        return a, None
+    idx = np.sort(np.random.default_rng(seed).choice(a.shape[0], cap, replace=False))
+    return a[idx], idx
+
+
+def tree_outputs(assignments, centroids=None) -> dict:
+    r"""What a caller of the timed path receives from the fitted tree, as float64 arrays: `assignments` = the cluster label
+    (1..K, largest cluster first) of every fingerprint (`get_assignments`), `cluster_sizes` = the size of cluster k at
+    k - 1, and - when the centroids are given (`get_centroids`, packed) - `centroids` of a seeded sample of the clusters
+    beside `centroids_clusters`, their labels.  An array longer than its cap is a fixed seeded sample of its rows, written
+    with `<name>_rows`, the row numbers taken: at most 57 MB in all."""
+    import numpy as np
+
+    labels = np.asarray(assignments).astype(np.int64)
+    out = {}
+    a, rows = _sample_rows(labels, 2_000_000, 1)
+    out["assignments"] = a.astype(np.float64)
+    if rows is not None:
+        out["assignments_rows"] = rows.astype(np.float64)
+    sizes, rows = _sample_rows(np.bincount(labels)[1:], 1_000_000, 2)
+    out["cluster_sizes"] = sizes.astype(np.float64)
+    if rows is not None:
+        out["cluster_sizes_rows"] = rows.astype(np.float64)
+    if centroids is not None and len(centroids):
+        k = len(centroids)
+        pick = np.arange(k) if k <= 4096 else np.sort(np.random.default_rng(3).choice(k, 4096, replace=False))
+        out["centroids"] = np.stack([np.asarray(centroids[i]) for i in pick]).astype(np.float64)
+        out["centroids_clusters"] = (pick + 1).astype(np.float64)
+    return out
+
+
+def write_outputs(directory: str, arrays: dict) -> None:
+    import numpy as np
+
+    total = sum(int(a.nbytes) for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs, the limit is {DUMP_LIMIT_BYTES}")
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(d / f"{name}.npy", a)
 
 
 _JSON_FD = 1
@@ -567,8 +637,10 @@ def multi_gpu(args: argparse.Namespace, world: int) -> None:
                       dtype=torch.int64, device=dev)
     ex_all = [torch.zeros_like(ex) for _ in range(world)]
     dist.all_gather(ex_all, ex)
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, tree_outputs(state["labels"]))
     cpu_mr = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # the same job on this host's cores: one shard file per rank with this rank's generator seeds, the oracle engine
         # under the file-based multiround host code (round 1 and the merge round's batches in process pools)
         import tempfile
@@ -636,8 +708,9 @@ def multi_gpu(args: argparse.Namespace, world: int) -> None:
                 "elements_per_launch": units / max(launches, 1),
                 "note": "latency/dependency-bound sequential insertion; 264 algorithmic bytes per inserted element",
             },
-            "cpu_baseline": cpu_mr,
         }
+        if args.full:
+            out["cpu_baseline"] = cpu_mr
         if cpu_mr is not None:
             # like for like: the GPU job on the very rows the CPU baseline was timed on - small trees on both sides;
             # `value` above is the job at `rows_per_shard`, whose per-row cost differs (larger trees), so no ratio is formed from it
@@ -698,54 +771,13 @@ def systolic_record(BitBirch, rows, default_tree, bf: int, thr: float, device: i
             os.environ["BBHIP_SYS"] = prev
 
 
-def single_gpu(args: argparse.Namespace) -> None:
+def single_gpu_full(args: argparse.Namespace, n: int, fps, one_step, lib, dev, local_rank: int) -> dict:
+    r"""`--full`: everything of the N = 1 line beyond the headline - the end-to-end step, the sub-records (other branching
+    factors, workloads, sizes and paths), the arr-vec and batched-compare kernels' own runs and the one-core CPU baselines."""
     import numpy as np
     import torch
 
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
-
     from bblean_amd import BitBirch, _lib
-
-    lib = _lib.load()
-    n = args.n_fps
-    gen = WORKLOADS[args.workload][0]
-    fps = gen(n, 1000, dev)  # resident in HBM
-    torch.cuda.synchronize()
-
-    def one_step() -> BitBirch:
-        tree = BitBirch(branching_factor=args.bf, threshold=args.threshold, merge_criterion="diameter",
-                        device=local_rank)
-        tree.fit(fps)
-        return tree
-
-    for _ in range(args.warmup):
-        one_step()
-    lib.bbh_profile_enable(1)
-    lib.bbh_profile_reset()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    tree = None
-    for _ in range(args.steps):
-        tree = one_step()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-
-    # every tree-kernel launch of the timed steps, the pipelined kernel's launches among them, and the one dominant launch
-    # (a fit is: a probe of the pipelined kernel on the empty tree, 8 192 elements of k_tree_fast, then ONE long launch)
-    all_launches, all_ms, all_units = _profile(lib, b"tree_insert")
-    k_launches, total_ms, units = _profile(lib, b"tree_insert/pipe")
-    dom_ms, dom_units = _longest(lib, b"tree_insert")
-    by_kernel = {name: dict(zip(("launches", "ms", "elements"), _profile(lib, b"tree_insert/" + name.encode())))
-                 for name in ("pipe", "fast", "complete")}
-    lib.bbh_profile_enable(0)
-    if units == 0:  # (a workload the pipelined kernel never took: the record is then about whatever did the work)
-        k_launches, total_ms, units = all_launches, all_ms, all_units
-    k_launches = max(k_launches, 1)
-    avg_ms = total_ms / k_launches
-    achieved = BYTES_PER_FP * units / (total_ms * 1e-3) / 1e9 if total_ms > 0 else 0.0
-    kc = tree._engine.kernel_counts()
 
     # fit + labels: the labels (get_assignments, reference bitbirch.py:1002-1047) on top of the timed fit
     torch.cuda.synchronize()
@@ -753,8 +785,7 @@ def single_gpu(args: argparse.Namespace) -> None:
     t_e2e = one_step()
     labels = t_e2e.get_assignments()
     e2e = time.perf_counter() - t1
-    n_clusters = int(labels.max())
-    del t_e2e
+    del t_e2e, labels
 
     # bf 254 is the default of `bb run` / `bb multiround` (BASELINE configs 3-5): the same rows into one tree at bf 254
     bf254 = None
@@ -1127,6 +1158,99 @@ def single_gpu(args: argparse.Namespace) -> None:
         except Exception as exc:  # the sub-record must not take the headline down with it
             dist_one = {"error": repr(exc)[:200]}
 
+    return {
+        "end_to_end": {
+            "seconds": e2e, "fingerprints_per_s": n / e2e,
+            "note": "one extra step: BitBirch.fit + get_assignments() (leaf export, member lists, labels 1..K)",
+        },
+        "k1_roofline": {
+            "kernel": "k_arr_vec<16,true> (arr-vec Tanimoto, 264 B/row)",
+            "bound": "hbm",
+            "achieved": k1_gbs,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": k1_gbs / HBM_PEAK_GBS,
+            "rows": k1_rows,
+            "avg_launch_ms": k1_ms,
+            "achieved_repeats": k1_repeats,
+        },
+        "k2_valu": {
+            "kernel": "k_best_match<64> (batched node compare, exact first-argmax)",
+            "bound": "valu",
+            "achieved": k2_laneops / 1e12,
+            "peak": k2_peak / 1e12,
+            "unit": "T lane-ops/s",
+            "frac": k2_laneops / k2_peak,
+            "queries": nq2, "centroids": nc2, "avg_launch_ms": k2_ms,
+        },
+        "bf254": bf254,
+        "other_workloads": others,
+        "config3": config3,
+        "merge_round": merge_round,
+        "bf1000": bf1000,
+        "cpu_baseline_bf254": cpu254,
+        "scale_anchor": scale_anchor,
+        "distributed_one_rank": dist_one,
+        "concurrent_shards": shard_stats,
+        "multiround_one_gpu": mr_stats,
+        "cpu_multiround_baseline": cpu_mr,
+    }
+
+
+
+def single_gpu(args: argparse.Namespace) -> None:
+    import torch
+
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+
+    from bblean_amd import BitBirch, _lib
+
+    lib = _lib.load()
+    n = args.n_fps
+    gen = WORKLOADS[args.workload][0]
+    fps = gen(n, 1000, dev)  # resident in HBM
+    torch.cuda.synchronize()
+
+    def one_step() -> BitBirch:
+        tree = BitBirch(branching_factor=args.bf, threshold=args.threshold, merge_criterion="diameter",
+                        device=local_rank)
+        tree.fit(fps)
+        return tree
+
+    for _ in range(args.warmup):
+        one_step()
+    lib.bbh_profile_enable(1)
+    lib.bbh_profile_reset()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    tree = None
+    for _ in range(args.steps):
+        tree = one_step()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+
+    # every tree-kernel launch of the timed steps, the pipelined kernel's launches among them, and the one dominant launch
+    # (a fit is: a probe of the pipelined kernel on the empty tree, 8 192 elements of k_tree_fast, then ONE long launch)
+    all_launches, all_ms, all_units = _profile(lib, b"tree_insert")
+    k_launches, total_ms, units = _profile(lib, b"tree_insert/pipe")
+    dom_ms, dom_units = _longest(lib, b"tree_insert")
+    by_kernel = {name: dict(zip(("launches", "ms", "elements"), _profile(lib, b"tree_insert/" + name.encode())))
+                 for name in ("pipe", "fast", "complete")}
+    lib.bbh_profile_enable(0)
+    if units == 0:  # (a workload the pipelined kernel never took: the record is then about whatever did the work)
+        k_launches, total_ms, units = all_launches, all_ms, all_units
+    k_launches = max(k_launches, 1)
+    avg_ms = total_ms / k_launches
+    achieved = BYTES_PER_FP * units / (total_ms * 1e-3) / 1e9 if total_ms > 0 else 0.0
+    kc = tree._engine.kernel_counts()
+
+    n_clusters = tree._engine.leaf_count()
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, tree_outputs(tree.get_assignments(), tree.get_centroids()))
+    full = single_gpu_full(args, n, fps, one_step, lib, dev, local_rank) if args.full else {}
+
     # HBM traffic of the tree kernel: NOT measured in this run - PMC counters need rocprofv3 (separate passes,
     # tools/profile_bench.sh); the committed measurement is only quoted when it was taken on this very kernel source
     traffic, traffic_source = None, None
@@ -1184,7 +1308,7 @@ def single_gpu(args: argparse.Namespace) -> None:
             # how much of the chip the tree kernels keep busy: the headline's pipelined kernel is ONE workgroup of 256 CUs by
             # construction (a single tree's insertions are one dependency chain); the opt-in level-systolic kernel spreads one
             # tree over its levels' owners (other_workloads.*.systolic_opt_in)
-            "workgroups_busy": workgroups_busy(others),
+            "workgroups_busy": workgroups_busy(full.get("other_workloads")),
             "by_kernel": by_kernel,
             "last_fit_elements_by_kernel": {"pipe": int(kc[0]), "fast": int(kc[1]), "complete": int(kc[2]),
                                             "unsupported_shape_stops": int(kc[6])},
@@ -1192,50 +1316,17 @@ def single_gpu(args: argparse.Namespace) -> None:
                     "pipelined kernel's elements x 264 B / its summed launch time (HIP events on the launch stream); "
                     "`dominant_launch` = the single longest tree-kernel launch of the timed steps",
         },
-        "end_to_end": {
-            "seconds": e2e, "fingerprints_per_s": n / e2e,
-            "note": "one extra step: BitBirch.fit + get_assignments() (leaf export, member lists, labels 1..K)",
-        },
-        "k1_roofline": {
-            "kernel": "k_arr_vec<16,true> (arr-vec Tanimoto, 264 B/row)",
-            "bound": "hbm",
-            "achieved": k1_gbs,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": k1_gbs / HBM_PEAK_GBS,
-            "rows": k1_rows,
-            "avg_launch_ms": k1_ms,
-            "achieved_repeats": k1_repeats,
-        },
-        "k2_valu": {
-            "kernel": "k_best_match<64> (batched node compare, exact first-argmax)",
-            "bound": "valu",
-            "achieved": k2_laneops / 1e12,
-            "peak": k2_peak / 1e12,
-            "unit": "T lane-ops/s",
-            "frac": k2_laneops / k2_peak,
-            "queries": nq2, "centroids": nc2, "avg_launch_ms": k2_ms,
-        },
-        "bf254": bf254,
-        "other_workloads": others,
-        "config3": config3,
-        "merge_round": merge_round,
-        "bf1000": bf1000,
-        "cpu_baseline_bf254": cpu254,
-        "scale_anchor": scale_anchor,
-        "distributed_one_rank": dist_one,
-        "concurrent_shards": shard_stats,
-        "multiround_one_gpu": mr_stats,
-        "cpu_multiround_baseline": cpu_mr,
     }
-    if not args.no_cpu:
-        sample = n if args.cpu_sample is None else min(args.cpu_sample, n)
-        out["cpu_baseline"] = cpu_baseline(fps[:sample].cpu().numpy(), args.bf, args.threshold)
-    else:
-        out["cpu_baseline"] = None
-    if args.workload == "fake" and n == 1_000_000 and args.bf == 50:
-        out["regressions"] = regressions(out, [REPO / "profiles" / PREVIOUS_ROUND / "bench_line_final.json",
-                                               REPO / f"BENCH_{PREVIOUS_ROUND}.json"])
+    if args.full:
+        out.update(full)
+        if not args.no_cpu:
+            sample = n if args.cpu_sample is None else min(args.cpu_sample, n)
+            out["cpu_baseline"] = cpu_baseline(fps[:sample].cpu().numpy(), args.bf, args.threshold)
+        else:
+            out["cpu_baseline"] = None
+        if args.workload == "fake" and n == 1_000_000 and args.bf == 50:
+            out["regressions"] = regressions(out, [REPO / "profiles" / PREVIOUS_ROUND / "bench_line_final.json",
+                                                   REPO / f"BENCH_{PREVIOUS_ROUND}.json"])
     _emit(out)
 
 

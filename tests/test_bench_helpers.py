@@ -1,9 +1,11 @@
 r"""CPU: bench.py's `regressions` record (every throughput of a line against the previous round's committed line) on the two
 lines that motivated it - round 4's against round 3's lists exactly the two regressions round 4 shipped without noticing -
-and the distributed exchange's one definition of a packed tail row's size."""
+the distributed exchange's one definition of a packed tail row's size, and the benchmark's options and output dump."""
 import json
 import sys
 from pathlib import Path
+
+import pytest
 
 REPO = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(REPO))
@@ -110,3 +112,45 @@ def test_workgroups_busy_record():
     assert out["systolic_opt_in_zipf_bf50"] == {"workgroups_resident": 97, "parallel_workgroups": 5.5, "identical_to_default_path": True}
     assert "systolic_opt_in_zipf_bf254" not in out and "systolic_opt_in_ecfp_bf50" not in out
     assert bench.workgroups_busy(None) == {"headline_kernel": 1, "compute_units": 256}
+
+
+def test_dump_outputs_are_float_bounded_and_seeded(tmp_path):
+    r"""`--dump-outputs`: float64 arrays, labels / sizes / centroids as the tree gives them; outputs larger than their caps are
+    the same seeded sample every time, and the whole dump stays under 64 MB."""
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(0)
+    labels = rng.integers(1, 38, size=1000).astype(np.uint64)
+    cents = [rng.integers(0, 256, size=256, dtype=np.uint8) for _ in range(37)]
+    out = bench.tree_outputs(labels, cents)
+    assert set(out) == {"assignments", "cluster_sizes", "centroids", "centroids_clusters"}
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert (out["assignments"] == labels).all() and out["cluster_sizes"].sum() == 1000
+    assert (out["centroids"] == np.stack(cents)).all() and (out["centroids_clusters"] == np.arange(1, 38)).all()
+    bench.write_outputs(str(tmp_path / "d"), out)
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == sorted(f"{k}.npy" for k in out)
+    assert (np.load(tmp_path / "d" / "assignments.npy") == out["assignments"]).all()
+
+    big = np.arange(2_500_000, dtype=np.uint64) % 1_200_000 + 1
+    many = [np.full(256, i % 256, dtype=np.uint8) for i in range(5000)]
+    a, b = bench.tree_outputs(big, many), bench.tree_outputs(big, many)
+    assert all((a[k] == b[k]).all() for k in a)
+    assert a["assignments"].shape == (2_000_000,) and (a["assignments"] == big[a["assignments_rows"].astype(np.int64)]).all()
+    assert a["cluster_sizes"].shape == (1_000_000,) and a["centroids"].shape == (4096, 256)
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES
+    with pytest.raises(TypeError):
+        bench.write_outputs(str(tmp_path / "e"), {"x": np.zeros(3, dtype=np.int64)})
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "e"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+
+
+def test_bench_options():
+    r"""`--full` and `--dump-outputs` exist; `--steps` below 1 is refused before anything runs."""
+    import subprocess
+
+    help_ = subprocess.run([sys.executable, str(REPO / "bench.py"), "--help"], capture_output=True, text=True, check=True).stdout
+    assert "--full" in help_ and "--dump-outputs" in help_
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "0", "--dry-run"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -7,10 +7,12 @@ fit -> set_merge(tolerance-diameter, tol 0.05) -> refine_inplace(n_largest=1).
 
 Times the HIP engine on N rows; when check_n > 0 the first check_n rows are also run through
 the CPU oracle with the same host logic and the cluster ids compared."""
+import os
 import sys
 import time
 
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 

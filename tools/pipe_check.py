@@ -2,7 +2,8 @@
     python tools/pipe_check.py [rows] [bf ...]"""
 import os, sys, time
 os.environ.pop("BBHIP_LAUNCH_LOG", None)  # (any value, "0" included, turns the log on)
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch
 from bench import WORKLOADS

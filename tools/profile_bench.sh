@@ -1,18 +1,19 @@
 #!/usr/bin/env bash
-# Runs on the GPU box (via gpurun): rocprofv3 kernel-trace stats of bench.py, then separate
+# Runs on the GPU machine: rocprofv3 kernel-trace stats of `bench.py --full`, then separate
 # PMC passes (FETCH_SIZE / WRITE_SIZE) as MI355X_MICROARCH.md prescribes.  Summaries land
-# under gpurun_out/prof_<tag>/ ; copy what should be judged into profiles/.
+# under $BB_OUT/prof_<tag>/ (default evidence/ in the repository); copy what should be judged into profiles/.
 set -uo pipefail
 TAG="${1:-r02}"
 NFPS="${2:-200000}"
 K1ROWS="${3:-8000000}"   # the arr-vec kernel is profiled on an array larger than the 256 MiB Infinity Cache
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
-FINAL="$ROOT/gpurun_out/prof_$TAG"
+FINAL="${BB_OUT:-$ROOT/evidence}/prof_$TAG"
 OUT="/tmp/prof_$TAG"
 rm -rf "$OUT"; mkdir -p "$OUT" "$FINAL"
+FINAL="$(cd "$FINAL" && pwd)"
 export TMPDIR=/tmp
 cd /tmp
-CMD="python $ROOT/bench.py --steps 1 --warmup 0 --n-fps $NFPS --no-cpu --shards 0 --multiround-files 0 --no-extras --k1-rows $K1ROWS"
+CMD="python $ROOT/bench.py --full --steps 1 --warmup 0 --n-fps $NFPS --no-cpu --shards 0 --multiround-files 0 --no-extras --k1-rows $K1ROWS"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- $CMD > "$OUT/bench_trace.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o bench -- $CMD > "$OUT/bench_pmc_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o bench -- $CMD > "$OUT/bench_pmc_write.log" 2>&1
