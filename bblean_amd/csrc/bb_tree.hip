@@ -35,8 +35,7 @@
 // All decisions use exact integers; the only floating point is the reference's own f64
 // formulae in the same operation order.
 //
-// Also here: the exact batch mode for one tree (k_route / k_upd + bb_tree_batch.inc, DESIGN.md
-// section 6b), many independent trees per launch (one or two workgroups per CU), the streaming
+// Also here: many independent trees per launch (one or two workgroups per CU), the streaming
 // ingest of host / file-backed rows (HostSlabs) and the leaf export kernels.
 #include "bb_common.h"
 
@@ -93,7 +92,6 @@ enum StopReason : int32_t {
     STOP_CF32 = 5,
     STOP_DEPTH = 6,
     STOP_RANGE = 7,  // n_samples would exceed 2^32-1
-    STOP_GATE = 8,   // a gate node would have to split inside a concurrent batch (admission bug), or a sealed node was met there
 };
 
 enum Ctr : int { C_NODES = 0, C_IDS, C_N8, C_N16, C_N32, C_ROOT, C_FIRST_LEAF, C_DEPTH, C_COUNT };
@@ -102,7 +100,7 @@ struct __attribute__((aligned(16))) RowMeta {
     uint32_t sub;   // BitFeature id (leaf rows; NONE for tracking rows)
     uint32_t n;     // n_samples
     uint32_t slot;  // tier << 30 | index into cf8/cf16/cf32
-    uint32_t pad;   // tracking rows: flip distance + 0 = unknown (see k_fd), else unused
+    uint32_t pad;   // unused (zero)
     unsigned long long s1;  // sum(ls)      (leaf rows)
     unsigned long long s2;  // sum(ls^2)    (leaf rows)
 };
@@ -1058,8 +1056,9 @@ __device__ __forceinline__ bool merge_accept(const KCt& k, const Elem& el, int& 
 }
 
 // Allocation of ids / slots / nodes.  Single-tree launches own the tree: the counters are
-// wave-uniform registers.  In SUB (concurrent gates of one tree) mode the counters live in the
-// TreeDev and are bumped with one device-scope atomic by thread 0, broadcast through LDS.
+// wave-uniform registers.  In SUB mode (the split cascade of k_tree_sys, bb_tree_sys.inc: many
+// workgroups allocate from one tree) the counters live in the TreeDev and are bumped with one
+// device-scope atomic by thread 0, broadcast through LDS.
 template <bool SUB, class KCt>
 __device__ __forceinline__ uint32_t alloc_n(const KCt& k, uint32_t& reg, uint32_t* gctr, uint32_t cnt, int bc_slot) {
     if constexpr (!SUB) {
@@ -1346,7 +1345,8 @@ __device__ __forceinline__ void split_node(const KCt& k, const Elem& el, int& re
         bc[10] = slotB_i;
         // word-granular header writes: a node's `next` word is only ever written by the split of
         // the node that follows it in the chain, every other word only by its own subtree, so
-        // concurrent gates never race on the leaf chain
+        // workgroups that split in different subtrees of one tree (SUB: k_tree_sys) never race
+        // on the leaf chain
         u32x4_t h = hold;
         h.y &= HW_LEAF;
         u32x4_t h1;
@@ -1562,7 +1562,6 @@ __device__ __forceinline__ void update_tracker_slow(const KCt& k, const Elem& el
     if (n_new > 0xFFFFFFFFull) stop = STOP_RANGE;
     if (tid == 0) {
         stg<uint32_t>((uint8_t*)(k.rm + pm) + 4, (uint32_t)n_new);
-        stg<uint32_t>((uint8_t*)(k.rm + pm) + 12, 0u);  // flip distance now stale
         stg<uint32_t>(k.card + pm, (uint32_t)cc[0]);
     }
 }
@@ -1612,10 +1611,9 @@ __device__ __forceinline__ uint32_t thaw_node(const KCt& k, uint32_t nd, uint32_
 // one tree per workgroup.  ONE: the cold path of the fast kernel (bb_tree_fast.inc) - insert exactly element
 // `e_first` of tree `trees`; allocation counters and statistics live in LDS (o.ctr / o.stats) across calls, the
 // stop reason and the number of processed elements are returned through o.ctr[8] / o.ctr[9].
-template <bool PROF, bool SUB, class KCt, bool ONE = false>
-__device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDev* trees, const uint32_t* gate_nodes,
-                                                 const uint32_t* gate_off, const uint32_t* gate_elems, long long e_first = 0) {
-    TreeDev* T = (SUB || ONE) ? trees : trees + blockIdx.x;
+template <bool PROF, class KCt, bool ONE = false>
+__device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDev* trees, long long e_first = 0) {
+    TreeDev* T = ONE ? trees : trees + blockIdx.x;
     uint32_t* gctr = T->ctr;
     KCt k;
     k.cent = T->node_cent; k.card = T->node_card; k.link = T->node_link; k.rm = T->node_rm; k.hdr = T->node_hdr;
@@ -1631,8 +1629,7 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
     }
     const uint8_t* in_rows = T->rows;
     const long long row_stride = T->row_stride;
-    const uint32_t g_off = SUB ? uni(gate_off[blockIdx.x]) : 0u;
-    const long long n_elems = SUB ? (long long)(uni(gate_off[blockIdx.x + 1]) - g_off) : T->n_elems;
+    const long long n_elems = T->n_elems;
     uint32_t* out_leaf = T->out_leaf;
     const uint32_t cap_nodes = uni(T->cap_nodes), cap8 = uni(T->cap8), cap16 = uni(T->cap16), cap32 = uni(T->cap32);
     if constexpr (KCt::buf == 0) k.bufs = nullptr;
@@ -1658,9 +1655,9 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
         c32 = uni(lc[C_N32]); cRoot = uni(lc[C_ROOT]); cFirst = uni(lc[C_FIRST_LEAF]); cDepth = uni(lc[C_DEPTH]);
     } else {
         cN = uni(T->ctr[C_NODES]); cI = uni(T->ctr[C_IDS]); c8 = uni(T->ctr[C_N8]); c16 = uni(T->ctr[C_N16]);
-        c32 = uni(T->ctr[C_N32]); cRoot = SUB ? uni(gate_nodes[blockIdx.x]) : uni(T->ctr[C_ROOT]); cFirst = uni(T->ctr[C_FIRST_LEAF]);
+        c32 = uni(T->ctr[C_N32]); cRoot = uni(T->ctr[C_ROOT]); cFirst = uni(T->ctr[C_FIRST_LEAF]);
         cDepth = uni(T->ctr[C_DEPTH]);
-        if (tid < 8) stats[tid] = SUB ? 0ull : T->stats[tid];
+        if (tid < 8) stats[tid] = T->stats[tid];
     }
     for (int ch = tid; ch < k.RBc; ch += TB) sx[ch] = (u32x4_t)(0);  // padding bytes stay zero
     __syncthreads();
@@ -1682,7 +1679,7 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
     u32x4_t pf = (u32x4_t)(0);
     long long e = ONE ? e_first : 0;
     const long long e_end = ONE ? e_first + 1 : n_elems;
-    if (pf_ok && tid < k.RBc) pf = ldg<u32x4_t>(in_rows + (SUB ? (size_t)uni(gate_elems[g_off]) * (size_t)row_stride : (size_t)e * (size_t)row_stride) + (size_t)tid * 16);
+    if (pf_ok && tid < k.RBc) pf = ldg<u32x4_t>(in_rows + (size_t)e * (size_t)row_stride + (size_t)tid * 16);
 
     int stop = STOP_DONE;
     for (; e < e_end; ++e) {
@@ -1697,7 +1694,7 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         }
         // ---- capacity for the worst case of one insertion -------------------------------
-        if constexpr (!SUB) {
+        {  // (a scope of its own: the descent below has its own `depth`)
             const uint32_t depth = cDepth;
             if (depth + 2 >= (uint32_t)MAXD) { stop = STOP_DEPTH; break; }
             // (every level may split - a node each, and a new root - and every node of the path may have to be thawed first)
@@ -1712,7 +1709,7 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
         else root_len = uni(ldg<uint32_t>(k.hdr + root));
         Elem el;
         PHASE(14);
-        const long long eidx = SUB ? (long long)uni(gate_elems[g_off + e]) : e;  // position in the input array
+        const long long eidx = e;  // position in the input array
         el.idx = eidx;
         // ---- element: packed centroid into LDS, n, moments ------------------------------
         if (!bufmode) {
@@ -1722,7 +1719,7 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
                 if (tid < k.RBc) sx[tid] = pf;
                 PHASE(15);
                 if (e + 1 < e_end && tid < k.RBc) {
-                    const long long nidx = SUB ? (long long)uni(gate_elems[g_off + e + 1]) : e + 1;
+                    const long long nidx = e + 1;
                     pf = ldg<u32x4_t>(in_rows + nidx * row_stride + (size_t)tid * 16);
                 }
             } else if ((((uintptr_t)row) & 15) == 0 && (nb & 15) == 0) {
@@ -1774,12 +1771,12 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
             // ---- very first element of an empty tree: row 0 of the root leaf -------------
             const uint32_t tier = tier_for(el.nS);
             const bool lazy = el.nS == 1;  // one member: its cluster features are its centroid, no slot and nothing to write
-            const uint32_t s = alloc_n<SUB>(k, cI, gctr + C_IDS, 1, 14);
+            const uint32_t s = alloc_n<false>(k, cI, gctr + C_IDS, 1, 14);
             uint32_t slotw = SLOT_LAZY8;
             if (!lazy)
-                slotw = (tier << 30) | (tier == 0 ? alloc_n<SUB>(k, c8, gctr + C_N8, 1, 15)
-                                                  : (tier == 1 ? alloc_n<SUB>(k, c16, gctr + C_N16, 1, 15)
-                                                               : alloc_n<SUB>(k, c32, gctr + C_N32, 1, 15)));
+                slotw = (tier << 30) | (tier == 0 ? alloc_n<false>(k, c8, gctr + C_N8, 1, 15)
+                                                  : (tier == 1 ? alloc_n<false>(k, c16, gctr + C_N16, 1, 15)
+                                                               : alloc_n<false>(k, c32, gctr + C_N32, 1, 15)));
             if (tid == 0) {
                 stg<uint32_t>(k.hdr + root, 1u);
                 stats[3]++;
@@ -1831,7 +1828,6 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
                                                    (uint32_t)depth, fill, &anyc);
                     if (hw_cap(leaf) < k.rows) {
                         // a sealed node: nothing is written to it where it lies (bb_tree.hip, "Node storage")
-                        if constexpr (SUB) { bad = true; break; }  // (concurrent gates: the host thaws the whole tree first)
                         __syncthreads();  // (path_node / path_row of the level above were written by thread 0)
                         const uint32_t pP = depth > 0 ? uni(path_node[depth - 1]) : NONE, pj = depth > 0 ? uni(path_row[depth - 1]) : 0u;
                         nd = thaw_node(k, nd, pP, pj, cN, cRoot, cFirst);
@@ -1979,10 +1975,10 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
                 const uint32_t new_tier = tier_for(new_n) > old_tier ? tier_for(new_n) : old_tier;
                 uint32_t slotN = slotT;
                 if (new_tier != old_tier) {
-                    slotN = (new_tier << 30) | (new_tier == 1 ? alloc_n<SUB>(k, c16, gctr + C_N16, 1, 15)
-                                                              : alloc_n<SUB>(k, c32, gctr + C_N32, 1, 15));
+                    slotN = (new_tier << 30) | (new_tier == 1 ? alloc_n<false>(k, c16, gctr + C_N16, 1, 15)
+                                                              : alloc_n<false>(k, c32, gctr + C_N32, 1, 15));
                 } else if (nT == 1) {
-                    slotN = alloc_n<SUB>(k, c8, gctr + C_N8, 1, 15);  // the second member: the BitFeature gets its uint8 row (SLOT_LAZY8)
+                    slotN = alloc_n<false>(k, c8, gctr + C_N8, 1, 15);  // the second member: the BitFeature gets its uint8 row (SLOT_LAZY8)
                 }
                 uint8_t* crow = k.cent + (leafm + jl) * (size_t)k.RB;
                 u64 card = pcs[0];
@@ -2034,12 +2030,12 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
                 // append_subcluster (bitbirch.py:284-287): new leaf BitFeature
                 const uint32_t tier = tier_for(el.nS);
                 const bool lazy = el.nS == 1;  // (one member: its cluster features are its centroid, no slot and nothing to write)
-                const uint32_t s = alloc_n<SUB>(k, cI, gctr + C_IDS, 1, 14);
+                const uint32_t s = alloc_n<false>(k, cI, gctr + C_IDS, 1, 14);
                 uint32_t slotw = SLOT_LAZY8;
                 if (!lazy)
-                    slotw = (tier << 30) | (tier == 0 ? alloc_n<SUB>(k, c8, gctr + C_N8, 1, 15)
-                                                      : (tier == 1 ? alloc_n<SUB>(k, c16, gctr + C_N16, 1, 15)
-                                                                   : alloc_n<SUB>(k, c32, gctr + C_N32, 1, 15)));
+                    slotw = (tier << 30) | (tier == 0 ? alloc_n<false>(k, c8, gctr + C_N8, 1, 15)
+                                                      : (tier == 1 ? alloc_n<false>(k, c16, gctr + C_N16, 1, 15)
+                                                                   : alloc_n<false>(k, c32, gctr + C_N32, 1, 15)));
                 if (tid == 0) {
                     stg<uint32_t>(k.hdr + leafnode, leaflen + 1);
                     stats[3]++;
@@ -2086,7 +2082,6 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
                             }
                             if (tid == 0) {
                                 stg<uint32_t>((uint8_t*)(k.rm + pm) + 4, (uint32_t)n_new);
-                                stg<uint32_t>((uint8_t*)(k.rm + pm) + 12, 0u);  // flip distance now stale
                                 stg<uint32_t>(k.card + pm, pcs[1 + q]);
                                 if (q < MAXM && q < nm) lds<uint32_t>(k.L, k.o.rc_card)[(uint32_t)q * k.rows + jp] = pcs[1 + q];
                             }
@@ -2120,18 +2115,13 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
                         if (q == lvl && lvl == D && q < nm && mir_node[q] == nd) ms_valid = true;  // leaf mirror, appended row included
                 }
                 const uint32_t trk = lvl > 0 ? uni(path_slot[lvl - 1]) : NONE;
-                split_node<SUB, PROF>(k, el, red_slot, cmp_par, nd, ms, ms_valid, trk, cN, c32, cFirst, gctr, sph);
+                split_node<false, PROF>(k, el, red_slot, cmp_par, nd, ms, ms_valid, trk, cN, c32, cFirst, gctr, sph);
 #pragma unroll
                 for (int q = 0; q < MAXM; ++q) mir_node[q] = NONE;  // slot `ms` was used as workspace
                 const uint32_t node1 = uni(bc[0]), cardA = uni(bc[3]), cardB = uni(bc[4]);
                 const uint32_t nA = uni(bc[7]), nB = uni(bc[8]);
                 const uint32_t slotA = (2u << 30) | uni(bc[9]), slotB = (2u << 30) | uni(bc[10]);
                 if (uni(bc[11])) { range_bad = true; break; }
-                if (SUB && lvl == 0) {  // a gate may never split inside a concurrent batch
-                    range_bad = true;
-                    stop = STOP_GATE;
-                    break;
-                }
                 if (lvl == 0) {
                     // root split: new root holding the two tracking BitFeatures
                     const uint32_t nr = cN;
@@ -2174,12 +2164,7 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
         if (tid == 0 && out_leaf) stg<uint32_t>(out_leaf + eidx, out_id);
     }
     __syncthreads();
-    if constexpr (SUB) {
-        // concurrent gates of one tree: counters were bumped atomically; fold the statistics in
-        if (tid < 7 && tid != 5 && tid != 6) atomicAdd((unsigned long long*)&T->stats[tid], (unsigned long long)stats[tid] );
-        if (tid == 5) atomicAdd((unsigned long long*)&T->stats[5], (unsigned long long)stats[5]);
-        if (tid == 0 && stop != STOP_DONE) atomicMax(&T->stop_reason, stop);
-    } else if constexpr (ONE) {
+    if constexpr (ONE) {
         if (tid == 0) {
             LA uint32_t* lc = lds<uint32_t>(k.L, k.o.ctr);
             lc[C_NODES] = cN; lc[C_IDS] = cI; lc[C_N8] = c8; lc[C_N16] = c16; lc[C_N32] = c32;
@@ -2207,11 +2192,10 @@ __device__ __forceinline__ void tree_insert_body(unsigned char* smem_raw, TreeDe
 }
 
 // A single tree (or a few) wants the whole register file: one wave per SIMD, no spills.
-template <bool PROF, bool SUB, class KCt = KC>
-__global__ __launch_bounds__(TB) void k_tree_insert(TreeDev* trees, const uint32_t* gate_nodes, const uint32_t* gate_off,
-                                                    const uint32_t* gate_elems) {
+template <bool PROF, class KCt = KC>
+__global__ __launch_bounds__(TB) void k_tree_insert(TreeDev* trees) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    tree_insert_body<PROF, SUB, KCt>(smem_raw, trees, gate_nodes, gate_off, gate_elems);
+    tree_insert_body<PROF, KCt>(smem_raw, trees);
 }
 
 // More trees than compute units: two workgroups per CU (<= 256 VGPRs, 2 waves per SIMD) hide each
@@ -2219,7 +2203,7 @@ __global__ __launch_bounds__(TB) void k_tree_insert(TreeDev* trees, const uint32
 template <class KCt = KC>
 __global__ __launch_bounds__(TB, 2) void k_tree_insert_dense(TreeDev* trees) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
-    tree_insert_body<false, false, KCt>(smem_raw, trees, nullptr, nullptr, nullptr);
+    tree_insert_body<false, KCt>(smem_raw, trees);
 }
 
 #endif  // __HIPCC__ (bb_tree_fast.inc has its own host / device split)
@@ -2308,138 +2292,6 @@ __global__ __launch_bounds__(256) void k_pack_singletons(const uint8_t* __restri
 __global__ __launch_bounds__(256) void k_gather_n_col(const uint8_t* __restrict__ bufs, long long k, int F, uint8_t* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < k) out[i] = bufs[(size_t)i * ((size_t)F + 1) + (size_t)F];
-}
-
-// =======================================================================================
-// Batch mode (exact, rollback-free): a prefix of the pending fingerprints is routed through the
-// STABLE upper levels of the tree in parallel (k_route), the host admits the longest prefix for
-// which (G1) no tracking centroid of a stable node can flip (flip distance, k_upd) and (G2) no
-// gate (leaf-parent node) can overflow, then every gate inserts its own elements sequentially
-// (k_tree_insert<.., SUB>), all gates concurrently, and the stable trackers receive their
-// commutative cluster-feature sums (k_upd).  See DESIGN.md section 6b for the argument.
-// =======================================================================================
-struct RouteRec {
-    uint32_t gate, gate_len, leaf, leaf_len, sumlen, pad;
-    uint32_t node[4], row[4], fd[4];
-};
-
-__device__ __forceinline__ KC make_kc(TreeDev* T, unsigned char* smem_raw, int nm) {
-    KC k;
-    k.cent = T->node_cent; k.card = T->node_card; k.link = T->node_link; k.rm = T->node_rm; k.hdr = T->node_hdr;
-    k.scratch = T->scratch_cent; k.cf8 = T->cf8; k.cf16 = T->cf16; k.cf32 = T->cf32;
-    k.bufs = nullptr; k.width = 0;
-    k.F = (int)uni((uint32_t)T->F); k.nb = (int)uni((uint32_t)T->nbytes); k.RB = (int)uni((uint32_t)T->RB);
-    k.RBc = k.RB / 16; k.RBS = k.RB + 16;
-    k.bf = uni((uint32_t)T->bf); k.rows = k.bf + 1; k.nblk = node_blocks(k.rows);
-    k.crit = 0; k.tol_len = 0; k.thr = 0; k.tolerance = 0; k.tol = nullptr;
-    k.nm = nm;
-    k.L = (LA unsigned char*)smem_raw;
-    k.o = smem_layout((int)k.bf, k.RB, nm);
-    return k;
-}
-
-// one workgroup per pending fingerprint: greedy descent through G stable levels + the gate
-__global__ __launch_bounds__(TB) void k_route(TreeDev* T, long long first_idx, uint32_t G, RouteRec* out) {
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    const KC k = make_kc(T, smem_raw, 0);
-    const int tid = threadIdx.x;
-    const long long idx = first_idx + blockIdx.x;
-    const uint8_t* row = T->rows + idx * T->row_stride;
-    LA u32x4_t* sx = lds<u32x4_t>(k.L, k.o.x);
-    for (int ch = tid; ch < k.RBc; ch += TB) sx[ch] = (u32x4_t)(0);
-    __syncthreads();
-    for (int b = tid; b < k.nb; b += TB) lds<uint8_t>(k.L, k.o.x)[b] = ldg<uint8_t>(row + b);
-    __syncthreads();
-    const uint32_t pcx = lds_vec_popcount(k, k.o.x);
-    int cmp_par = 0;
-    uint32_t nd = uni(T->ctr[C_ROOT]);
-    uint32_t sumlen = 0;
-    RouteRec rec;
-    rec.pad = 0;
-#pragma unroll
-    for (int l = 0; l < 4; ++l) { rec.node[l] = NONE; rec.row[l] = 0; rec.fd[l] = 0; }
-    for (uint32_t l = 0; l <= G; ++l) {
-        uint32_t len = 0, leaf = 0;
-        const Cand best = node_best<false, false>(k, cmp_par, nd, -1, k.o.x, pcx, false, false, true, &len, &leaf);
-        const uint32_t link = uni(lds<uint32_t>(k.L, k.o.link)[cmp_par * k.rows + best.r]);
-        if (l < G) {
-            const uint32_t fd = uni(ldg<uint32_t>((const uint8_t*)(k.rm + (size_t)nd * NG + best.r) + 12));
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if ((uint32_t)q == l) { rec.node[q] = nd; rec.row[q] = best.r; rec.fd[q] = fd; }
-            sumlen += len;
-            nd = link;
-        } else {
-            rec.gate = nd;
-            rec.gate_len = len;
-            rec.leaf = link;
-            rec.leaf_len = uni(ldg<uint32_t>(k.hdr + link));
-        }
-    }
-    rec.sumlen = sumlen;
-    if (tid == 0) out[blockIdx.x] = rec;
-}
-
-// one workgroup per stable tracking row: CF += sum of the admitted fingerprints routed through
-// it (commutative), n += count, new centroid / popcount, and the row's flip distance
-//   fd = min over features of (2*ls >= n ? 2*ls - n + 1 : n - 2*ls)
-// = the smallest number of further single-fingerprint additions that could change any centroid
-// bit.  count == 0 just (re)computes fd.
-__global__ __launch_bounds__(TB) void k_upd(TreeDev* T, const uint32_t* u_node, const uint32_t* u_row,
-                                            const uint32_t* u_off, const uint32_t* u_elems, uint32_t* out_fd) {
-    __shared__ unsigned long long s_card[TW];
-    __shared__ uint32_t s_fd[TW];
-    const int tid = threadIdx.x;
-    const uint32_t F = (uint32_t)T->F, nb = (uint32_t)T->nbytes, RB = (uint32_t)T->RB;
-    const uint32_t nd = u_node[blockIdx.x], r = u_row[blockIdx.x];
-    const uint32_t e0 = u_off[blockIdx.x], e1 = u_off[blockIdx.x + 1];
-    const size_t m = (size_t)nd * NG + r;
-    RowMeta* rm = T->node_rm + m;
-    const uint32_t slot = rm->slot & 0x3FFFFFFFu;
-    const unsigned long long n_new = (unsigned long long)rm->n + (e1 - e0);
-    uint32_t* cf = T->cf32 + (size_t)slot * F;
-    const uint8_t* in_rows = T->rows;
-    const long long stride = T->row_stride;
-    unsigned long long card = 0;
-    uint32_t fd = 0xFFFFFFFEu;
-    for (uint32_t b = tid; b < nb; b += TB) {
-        uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t e = e0; e < e1; ++e) {
-            const uint32_t v = in_rows[(long long)u_elems[e] * stride + b];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc[q] += (v >> (7 - q)) & 1u;
-        }
-        uint32_t byte = 0;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const unsigned long long v = (unsigned long long)cf[b * 8 + q] + acc[q];
-            cf[b * 8 + q] = (uint32_t)v;
-            const bool bit = n_new <= 1 ? ((v & 0xFF) != 0) : (2ull * v >= n_new);
-            byte |= (bit ? 1u : 0u) << (7 - q);
-            const unsigned long long d = 2ull * v >= n_new ? 2ull * v - n_new + 1ull : n_new - 2ull * v;
-            const uint32_t dd = d > 0xFFFFFFFEull ? 0xFFFFFFFEu : (uint32_t)d;
-            fd = dd < fd ? dd : fd;
-        }
-        T->node_cent[m * RB + b] = (uint8_t)byte;
-        card += __popc(byte);
-    }
-    for (int o = 32; o >= 1; o >>= 1) {
-        card += (unsigned long long)__shfl_xor((long long)card, o);
-        const uint32_t of = (uint32_t)__shfl_xor((int)fd, o);
-        fd = of < fd ? of : fd;
-    }
-    if ((tid & 63) == 0) { s_card[tid >> 6] = card; s_fd[tid >> 6] = fd; }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned long long c = 0;
-        uint32_t f = 0xFFFFFFFEu;
-        for (int w = 0; w < TW; ++w) { c += s_card[w]; f = s_fd[w] < f ? s_fd[w] : f; }
-        if (n_new > 0xFFFFFFFFull) atomicMax(&T->stop_reason, (int)STOP_RANGE);
-        rm->n = (uint32_t)n_new;
-        rm->pad = f;
-        T->node_card[m] = (uint32_t)c;
-        if (out_fd) out_fd[blockIdx.x] = f;
-    }
 }
 
 // ---- extraction ---------------------------------------------------------------------------
@@ -2578,7 +2430,6 @@ struct bbh_tree {
     // node-pool compactions (gc_nodes): how many ran, nodes they sealed / left at full capacity (last one), blocks before / after (last one)
     uint64_t gc_runs = 0, gc_sealed = 0, gc_full = 0, gc_before = 0, gc_after = 0;
     bool lazy_pools = false;  // a fresh tree owns no pools yet: the first call that inserts allocates them at the size it needs (pregrow)
-    bool no_seal = false;  // (while the exact batch mode runs: compactions leave every node at full capacity)
     size_t peak_bytes = 0;  // largest sum of this tree's pool allocations (both copies of a pool that is being regrown included)
     // the level-systolic kernel (bb_tree_sys.inc): its work area in HBM (rings, mailboxes), how many blocks the mailbox arrays hold,
     // and what it did: elements, launches, relaunches after a root split, workgroups of the last launch, summed busy cycles of
@@ -2722,7 +2573,7 @@ static size_t gc_min_bytes() {
 // length rounded up to a block, the others at full capacity; blocks that thaw_node gave up disappear.  Ids change: child
 // ids, the leaf chain, the root and the first leaf are translated; nothing on the host outlives a call with node ids in it
 // except the leaf chain's copy, which is dropped.  The new pools hold what is live afterwards plus `extra` blocks, or a
-// quarter more if that is more.  seal == 0 brings every node back to full capacity (the exact batch mode wants that).
+// quarter more if that is more.  seal == 0 brings every node back to full capacity (bbh_tree_compact).
 int gc_nodes(bbh_tree* t, uint64_t extra, int seal) {
     TreeDev& h = t->h;
     const uint32_t used = std::min(h.cap_nodes, h.ctr[C_NODES]);
@@ -2820,7 +2671,7 @@ int grow_nodes(bbh_tree* t, uint32_t want, uint64_t gc_extra = 0) {  // (gc_extr
     // 16-byte header (a multiround round creates hundreds of trees and grows each of them once)
     const bool pristine = h.ctr[C_NODES] == nblk && h.ctr[C_IDS] == 0 && h.stats[3] == 0;
     const uint32_t used = std::min(h.cap_nodes, h.ctr[C_NODES]);
-    if (!pristine && h.cap_nodes > 0 && (size_t)used * block_bytes(h) >= gc_min_bytes()) return gc_nodes(t, gc_extra ? gc_extra : (uint64_t)want - used, t->no_seal ? 0 : 1);
+    if (!pristine && h.cap_nodes > 0 && (size_t)used * block_bytes(h) >= gc_min_bytes()) return gc_nodes(t, gc_extra ? gc_extra : (uint64_t)want - used, 1);
     {
         const uint32_t floor_elems = clamp30((uint64_t)h.ctr[C_NODES] + (2 * (uint64_t)h.ctr[C_DEPTH] + 64) * nblk);
         want = fit_to_memory(grow_target(h.cap_nodes, want), std::max(floor_elems, h.cap_nodes + 1), h.cap_nodes, block_bytes(h));
@@ -2942,11 +2793,10 @@ int configure(bbh_tree* t, int32_t bf, int32_t n_features) {
             // (gfx950: 160 KiB per workgroup; elsewhere - BBHIP_ALLOW_ANY_ARCH - whatever a compute unit has)
             const bool is950 = std::strncmp(prop.gcnArchName, "gfx950", 6) == 0;
             const int cap = is950 ? 160 * 1024 : (int)std::min<size_t>(prop.maxSharedMemoryPerMultiProcessor, 160 * 1024);
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+            BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+            BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert<true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
             BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert_dense<KC>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert<true, false, KC50>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+            BB_HIP(hipFuncSetAttribute((const void*)k_tree_insert<true, KC50>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
             // the steady-state / pipelined kernels use the CU's whole LDS whatever this tree's own layout needs
             if ((uint32_t)cap >= pipe_layout(254).total && (uint32_t)cap >= fast_layout(254).total) {
                 for (const FastKernel& fk : kFastKernels)
@@ -3453,14 +3303,12 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
                 log_kernel = "fast";
                 hipLaunchKernelGGL(fk->fn, grid, block, fk->lds, s, dptr);
             } else if (prof_phases) {
-                const uint32_t* const nu = nullptr;
-                if (all50) hipLaunchKernelGGL((k_tree_insert<true, false, KC50>), grid, block, lds, s, dptr, nu, nu, nu);
-                else hipLaunchKernelGGL((k_tree_insert<true, false>), grid, block, lds, s, dptr, nu, nu, nu);
+                if (all50) hipLaunchKernelGGL((k_tree_insert<true, KC50>), grid, block, lds, s, dptr);
+                else hipLaunchKernelGGL((k_tree_insert<true>), grid, block, lds, s, dptr);
             } else {
                 // the complete engine, shape as run-time values; two workgroups per CU when there are more trees than CUs
-                const uint32_t* const nu = nullptr;
                 if (dense_launch(active.size(), lds)) hipLaunchKernelGGL(k_tree_insert_dense<KC>, grid, block, lds, s, dptr);
-                else hipLaunchKernelGGL((k_tree_insert<false, false, KC>), grid, block, lds, s, dptr, nu, nu, nu);
+                else hipLaunchKernelGGL((k_tree_insert<false, KC>), grid, block, lds, s, dptr);
             }
             e = hipGetLastError();
         }
@@ -3720,8 +3568,6 @@ int run_insert(bbh_tree* t, const uint8_t* rows_dev, int64_t row_stride, const u
 }
 
 
-#include "bb_tree_batch.inc"
-
 // walk the leaf chain on the host (bitbirch.py:886-893): positions -> (node, row)
 int build_chain(bbh_tree* t) {
     if (t->chain_valid) return BBH_OK;
@@ -3941,11 +3787,8 @@ extern "C" int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, 
     BB_TRY(pregrow(t, n, 0));
     bb::DevOut o;
     BB_TRY(o.init(out_leaf, (size_t)n * 4));
-    const char* benv = getenv("BBHIP_BATCH");
-    const int batch = benv ? atoi(benv) : 0;
     if (bb::is_device_ptr(rows)) {
-        if (batch > 0) BB_TRY(run_insert_batched(t, rows, row_stride, n, (uint32_t*)o.dev, batch, s));
-        else BB_TRY(run_insert(t, rows, row_stride, nullptr, 0, n, (uint32_t*)o.dev, s));
+        BB_TRY(run_insert(t, rows, row_stride, nullptr, 0, n, (uint32_t*)o.dev, s));
     } else {
         HostSlabs slabs;
         BB_TRY(slabs.init(t->device, rows, (size_t)row_stride, n));
@@ -3954,8 +3797,7 @@ extern "C" int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, 
             int64_t m = 0;
             BB_TRY(slabs.acquire(off, &d, &m));
             uint32_t* o_off = o.dev ? (uint32_t*)o.dev + off : nullptr;
-            if (batch > 0) BB_TRY(run_insert_batched(t, d, row_stride, m, o_off, batch, s));
-            else BB_TRY(run_insert(t, d, row_stride, nullptr, 0, m, o_off, s));
+            BB_TRY(run_insert(t, d, row_stride, nullptr, 0, m, o_off, s));
             off += m;
         }
     }

@@ -132,7 +132,7 @@ struct KCold : KCBase {
 
 template <int BF>
 __device__ __attribute__((noinline)) void cold_insert_one(unsigned char* smem_raw, TreeDev* T, long long e) {
-    tree_insert_body<false, false, KCold<BF>, true>(smem_raw, T, nullptr, nullptr, nullptr, e);
+    tree_insert_body<false, KCold<BF>, true>(smem_raw, T, e);
 }
 
 // The same context with the one mirror slot pointed at an arbitrary slot of the fast kernel (run-time offsets).
@@ -1123,7 +1123,6 @@ __device__ __forceinline__ long long fast_run(unsigned char* smem_raw, TreeDev* 
                 if (slotted) *(LA uint8_t*)(L + sb + __umul24(p_row[q], FRBS) + tid) = (uint8_t)byteT[q];
                 if (tid == 64 * ((q + 1) & 3)) {
                     stg<uint32_t>((uint8_t*)(k.rm + pm) + 4, n_new);
-                    stg<uint32_t>((uint8_t*)(k.rm + pm) + 12, 0u);  // flip distance of the batch mode: stale
                     stg<uint32_t>(k.card + pm, pcs[1 + q]);
                     if (slotted) {
                         *(LA uint32_t*)(L + sb + f.s_rm + p_row[q] * 32 + 4) = n_new;

@@ -62,7 +62,6 @@ enum PipeSplit : int { PS_LEAF = 0, PS_P, PS_JP, PS_LENP, PS_TRK, PS_POP, PS_XOF
 // control words (u32 indices into PSmem::ctl)
 enum PipeCtl : int { PC_HEAD = 0, PC_TAIL, PC_END, PC_ABORT, PC_REASON, PC_E_LO, PC_E_HI, PC_STOPCODE, PC_DCOUNT, PC_NZ, PC_PGO, PC_PLEN, PC_LGO, PC_PZERO,
                      PC_WM,  // (K::ML) the leaf engine's watermark: the global stores of every job below it have completed
-                     PC_DEC, // (K::DUAL) jobs whose merge-or-append decision is made, in job order (the ticket of the BitFeature ids)
                      PC_COUNT };
 static_assert(PC_COUNT <= 16, "the control block is 16 words");
 
@@ -175,21 +174,6 @@ static_assert(pipe_layout(50, 1).leaf0 == pipe_layout(50).leaf0 && pipe_layout(5
 #if defined(__HIPCC__)
 
 #define PIPE_SPIN_LIMIT (1u << 22)
-// pst words 12 / 13: the leaf that leaf slot 0 holds when a run starts (NONE: none) and its length - left by the run before
-// (its leaf engine's slot 0 at the end of the run; node1 after a leaf split, cold_leaf_split_p), cleared by whatever may have
-// changed the tree behind the slot's back (the complete engine between runs)
-constexpr int PST_KEEP = 12;
-// MEASURED AND SWITCHED OFF (round 5, -DBBH_KEEP_LEAF=1 builds it): exact (the pipeline's fuzz / audit tests ran green on
-// it) and the fill it saves is real - `leaf:fill` 751 -> 56 cycles per insertion on S-ecfp at bf 254, where every split
-// emptied the ONE leaf slot and the leaf engine then read back the 70 KB it had just written (22 k cycles) - but the fit got
-// 1.5 % SLOWER at bf 254 (S-ecfp 330 k -> 325 k/s) and 3.8 % at bf 50 with the first, barrier-per-pass compaction
-// (profiles/r05/ab_keep.txt, pipe_phases_ecfp_keep_1M.txt): while the leaf engine fills, the router queues eight jobs and
-// the helper waves pre-compare all of them against the fresh slot; with the slot there at once the first jobs of every
-// run are compared by the leaf engine itself (4.5 k instead of 1.75 k cycles each, "own" 0.16 -> 0.19 per insertion).
-#ifndef BBH_KEEP_LEAF
-#define BBH_KEEP_LEAF 0
-#endif
-template <int BF> constexpr bool PIPE_KEEP_LEAF = BBH_KEEP_LEAF != 0 && BF > 63;
 // Where a bounded wait of a launch gave up: the abort flag itself carries the line of this file (any non-zero value aborts),
 // the workgroup's thread 0 hands it to the host with STOP_INTERNAL (TreeDev::giveup_line).  Round 4 recorded it with an
 // atomicCAS on a device global inside every wait loop: never executed, but the bf 254 instances of the kernel ran 13 % slower
@@ -217,7 +201,7 @@ struct KColdP : KCBase {
 
 template <int BF>
 __device__ __attribute__((noinline)) void cold_insert_one_p(unsigned char* smem_raw, TreeDev* T, long long e) {
-    tree_insert_body<false, false, KColdP<BF>, true>(smem_raw, T, nullptr, nullptr, nullptr, e);
+    tree_insert_body<false, KColdP<BF>, true>(smem_raw, T, e);
 }
 
 // A leaf that overflowed, split where it lies (_split_node, bitbirch.py:162-211 + update_split_subclusters, :289-303): the
@@ -259,53 +243,8 @@ __device__ __attribute__((noinline)) void cold_leaf_split_p(unsigned char* smem_
         lctr[8] = bad ? (uint32_t)STOP_RANGE : (uint32_t)STOP_DONE;
     }
     __syncthreads();
-    // Leaf slot 0 still holds all bf + 1 rows in their old order: the rows that went to node1 - the node row jp of the parent
-    // goes on pointing at, where the next elements of this neighbourhood arrive - are moved up in place (a stable partition:
-    // a row's new index is never above its old one), their popcounts / slot words / records come from the split's staging
-    // arrays, and the next run's leaf engine is told that slot 0 holds node1 (PST_KEEP).  Until round 5 every run started with
-    // empty leaf slots: after each split the leaf engine read the 70 KB it had just written back from L2 (22 k cycles per
-    // split at bf 254, `leaf:fill` in profiles/r05/pipe_phases_ecfp_1M.txt).
-    constexpr PSmem pp = pipe_layout(BF);
-    if constexpr (!PIPE_KEEP_LEAF<BF>) {
-        if (tid == 0) *(LA uint32_t*)(k.L + pp.pst + PST_KEEP * 4) = NONE;
-        __syncthreads();
-    } else {
-        const uint32_t n1 = uni(bc[5]), m = n1 + uni(bc[6]);
-        LA uint32_t* dstv = lds<uint32_t>(k.L, k.o.dst);
-        LA uint32_t* mcard = lds<uint32_t>(k.L, k.o.mcard);
-        LA uint32_t* mlink = lds<uint32_t>(k.L, k.o.mlink);
-        LA u32x4_t* mrm = lds<u32x4_t>(k.L, k.o.mrm);
-        const uint32_t sb0 = f.slot0;
-        // (no barrier: wave w moves 16-byte pieces 4 w .. 4 w + 3 of every row, sixteen rows per step in ascending order - a
-        // wave's LDS accesses execute in order, a row never moves up, and the waves' bytes are disjoint)
-        const uint32_t wv = (uint32_t)tid >> 6, ln = (uint32_t)tid & 63u;
-        const uint32_t rr = ln >> 2, piece = wv * 4 + (ln & 3u);
-#pragma unroll 1
-        for (uint32_t r0 = 0; r0 < m; r0 += 16) {
-            const uint32_t r = r0 + rr;
-            const uint32_t d = r < m ? dstv[r] : 0u;
-            const bool mv = r < m && (d & 0x80000000u) != 0;
-            u32x4_t v = (u32x4_t)(0);
-            if (mv) v = *(LA u32x4_t*)(k.L + sb0 + r * FRBS + piece * 16);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the step's rows are in registers before any of them is overwritten)
-            if (mv) *(LA u32x4_t*)(k.L + sb0 + (d & 0x7FFFFFFFu) * FRBS + piece * 16) = v;
-        }
-        for (uint32_t r = (uint32_t)tid; r < m; r += TB) {
-            const uint32_t d = dstv[r];
-            if (d & 0x80000000u) {
-                const uint32_t q = d & 0x7FFFFFFFu;
-                *(LA uint32_t*)(k.L + sb0 + f.s_card + q * 4) = mcard[r];
-                *(LA uint32_t*)(k.L + sb0 + f.s_link + q * 4) = mlink[r];
-                *(LA u32x4_t*)(k.L + sb0 + f.s_rm + q * 32) = mrm[2 * r];
-                *(LA u32x4_t*)(k.L + sb0 + f.s_rm + q * 32 + 16) = mrm[2 * r + 1];
-            }
-        }
-        if (tid == 0) {
-            *(LA uint32_t*)(k.L + pp.pst + PST_KEEP * 4) = bad ? NONE : node1;
-            *(LA uint32_t*)(k.L + pp.pst + (PST_KEEP + 1) * 4) = n1;
-        }
-        __syncthreads();
-    }
+    // (the next run starts with empty leaf slots: keeping node1's rows in slot 0 for it was exact but 1.5 % slower at bf 254
+    // and 3.8 % at bf 50, profiles/r05/ab_keep.txt)
     if constexpr (PROF) {
         if (tid == 0) {  // (phase-timer build: the split's phases as wave 0 saw them)
             for (int i = 0; i < 8; ++i) T->splitprof[i] += sph[i];
@@ -323,29 +262,15 @@ struct KP {
     static constexpr uint32_t rows = BFv + 1, bf = BFv, nblk = node_blocks(BFv + 1);
     static constexpr int RPL = (BFv + 1 + 63) / 64;  // rows per lane in a node compare
     static constexpr int PW = pipe_pw(BFv), PREW = pipe_prew(BFv);
-#ifndef BBH_DUAL
-#define BBH_DUAL 0
-#endif
-    // BBH_DUAL=1 (compile-time, OFF by default): two leaf engines (waves 1 and 3) instead of one plus a helper that
-    // pre-compares for it - nodes of one row per lane: a job goes to the engine its leaf belongs to (leaf id parity), each
-    // engine owns half of the leaf slots and of the cluster-feature cache, BitFeature ids are handed out in job order through
-    // a ticket (PC_DEC), slots of the pools through LDS atomics; see pipe_leaf.  Exact (the parity suite passes with it) and
-    // measured in round 4: the leaf side's throughput doubles, the fit gets 5 % SLOWER (S-fake bf 50: 418 k vs 439 k
-    // fingerprints/s, profiles/r04/pipe_phases_variants_1M.txt) - the router, not the leaf engine, is what an insertion
-    // waits for (5.4 k cycles per element, 2 k of them serialised LDS round trips of its bookkeeping), and retiring the jobs
-    // of two engines from done marks costs it another 200.  Kept for the day the router is faster than one leaf engine.
-    static constexpr bool DUAL = BBH_DUAL != 0 && (BFv + 1 + 63) / 64 == 1 && MLv == 0;
-#ifndef BBH_CMT
-#define BBH_CMT 1
-#endif
-    // Several exact levels: the tracking updates of an element (CF += element, new majority centroid, one per exact level:
-    // bitbirch.py:352-357) are done by the HELPER waves - wave 3 the even levels (it does nothing else then: the first level's
-    // update is the one the router waits for first; the leaf pre-compares it does otherwise were never used with this router,
-    // whose leaf engine is waiting for jobs most of the time), wave 2 the odd ones - while the router goes on with the next
-    // element; it waits at every level of the way down until the level's update of the element before is in the slot.
-    // See pipe_commit_level / pipe_commit_try.
-    static constexpr bool CMT = BBH_CMT != 0 && ML && !DUAL;
-    static constexpr bool ASYNC_L = !DUAL;     // the leaf engine keeps row versions and publishes its slots (pre-compare by helper waves)
+    // (one leaf engine, helped by pre-compares of the other waves: two leaf engines were exact but 5 % slower, the router is
+    // what an insertion waits for - S-fake bf 50 418 k vs 439 k/s, profiles/r04/pipe_phases_variants_1M.txt)
+    // Several exact levels (ML): the tracking updates of an element (CF += element, new majority centroid, one per exact
+    // level: bitbirch.py:352-357) are done by the HELPER waves - wave 3 the even levels (it does nothing else then: the first
+    // level's update is the one the router waits for first; the leaf pre-compares it does otherwise were never used with this
+    // router, whose leaf engine is waiting for jobs most of the time), wave 2 the odd ones - while the router goes on with the
+    // next element; it waits at every level of the way down until the level's update of the element before is in the slot.
+    // See pipe_commit_level / pipe_commit_try.  (The router committing itself was 7 % slower: S-rdkit-like 158 k vs 171 k/s,
+    // profiles/r04/fit_workloads_1M.txt.)
 #ifndef BBH_PREWL
 #define BBH_PREWL 4
 #endif
@@ -677,7 +602,7 @@ __device__ __forceinline__ uint32_t centroid_dword31(const uint32_t (&v)[32], ui
     return out;
 }
 
-// ---- tracking updates by the helper waves (K::CMT) -----------------------------------------------------------------------
+// ---- tracking updates by the helper waves (K::ML) ------------------------------------------------------------------------
 // The mailbox: requests posted by the router (one per routed element: the number of levels, where the element's row is; the
 // levels' records {slot, row, cf32 slot word, n before, node} are the router's path entries, p.upath), per helper wave the
 // progress word (8 x request + levels of it done: written as soon as the row, its popcount and n are in the slot) and the
@@ -783,7 +708,6 @@ __device__ __forceinline__ void pipe_commit_level(LA unsigned char* L, TreeDev* 
     if (lane == 0) {
         stg<uint32_t>(T->node_card + prow, cardn);
         stg<uint32_t>((uint8_t*)(T->node_rm + prow) + 4, nnew);
-        stg<uint32_t>((uint8_t*)(T->node_rm + prow) + 12, 0u);  // flip distance of the batch mode: stale
     }
 }
 
@@ -846,17 +770,13 @@ __device__ __forceinline__ void pipe_prep(LA unsigned char* L, TreeDev* T, long 
         const long long ee = e0 + (long long)q;
         return ldg<uint32_t>(in_rows + (size_t)(ee < n_elems ? ee : n_elems - 1) * (size_t)row_stride + lane * 4);
     };
-#ifndef BBH_PREP_AHEAD
-#define BBH_PREP_AHEAD 1
-#endif
-    uint32_t xq0 = 0, xq1 = 0, xq2 = 0, xq3 = 0;
-    if constexpr (BBH_PREP_AHEAD != 0) { xq0 = row_load(0); xq1 = row_load(1); xq2 = row_load(2); xq3 = row_load(3); }
-    constexpr int NC0 = K::CMT ? (p.ntc + 1) / 2 : 1;  // (K::CMT) this wave's entries of the cache of tracking cluster features
+    uint32_t xq0 = row_load(0), xq1 = row_load(1), xq2 = row_load(2), xq3 = row_load(3);
+    constexpr int NC0 = K::ML ? (p.ntc + 1) / 2 : 1;  // (K::ML) this wave's entries of the cache of tracking cluster features
     PipeTcf<NC0> cst;
     pipe_tcf_init(cst);
 #pragma unroll 1
     while (true) {
-        if constexpr (K::CMT) {
+        if constexpr (K::ML) {
             // a tracking update the router has posted: before anything else (it is waited for)
             if (pipe_commit_try<K, 1, 0, NC0>(L, T, lane, cst)) { spins = 0; continue; }
         }
@@ -871,14 +791,9 @@ __device__ __forceinline__ void pipe_prep(LA unsigned char* L, TreeDev* T, long 
             continue;
         }
         spins = 0;
-        uint32_t xd;
-        if constexpr (BBH_PREP_AHEAD != 0) {
-            xd = xq0;
-            xq0 = xq1; xq1 = xq2; xq2 = xq3;
-            xq3 = row_load(i + 4);
-        } else {
-            xd = row_load(i);
-        }
+        const uint32_t xd = xq0;
+        xq0 = xq1; xq1 = xq2; xq2 = xq3;
+        xq3 = row_load(i + 4);
         const uint32_t xoff = p.xq + (i & (K::PW - 1)) * 256;
         *(LA uint32_t*)(L + xoff + lane * 4) = xd;
         const uint32_t pop = wsum32((uint32_t)__popc(xd));
@@ -889,7 +804,7 @@ __device__ __forceinline__ void pipe_prep(LA unsigned char* L, TreeDev* T, long 
         i += 1;
     }
     // the run is over (the router has seen its last request finished): the cached cluster features go back to HBM
-    if constexpr (K::CMT) pipe_tcf_flush<K, 0, NC0>(L, T, lane, cst);
+    if constexpr (K::ML) pipe_tcf_flush<K, 0, NC0>(L, T, lane, cst);
 }
 
 // One leaf pre-compare, if there is one to do: job j (the next one of this helper's parity that the leaf engine has not
@@ -960,11 +875,11 @@ __device__ __forceinline__ void pipe_prel(LA unsigned char* L, uint32_t parity, 
     }
 }
 
-// wave 3 when the helper waves commit (K::CMT): the even levels' tracking updates
+// wave 3 of the multi-level instance (K::ML): the even levels' tracking updates
 template <class K>
 __device__ __forceinline__ void pipe_prel_cmt(LA unsigned char* L, TreeDev* T) {
     constexpr PSmem p = K::p;
-    constexpr int NC0 = (p.ntc + 1) / 2, NC1 = K::CMT ? p.ntc - NC0 : 1;  // (instantiated for every K, called if K::CMT)
+    constexpr int NC0 = (p.ntc + 1) / 2, NC1 = K::ML ? p.ntc - NC0 : 1;  // (instantiated for every K, called if K::ML)
     static_assert(NC1 >= 1, "both committing waves need a cache entry");
     const uint32_t lane = (uint32_t)ftid() & 63u;
     PipeTcf<NC1> cst;
@@ -1323,7 +1238,6 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
 #pragma unroll
         for (int q = 0; q < RPL; ++q) *(LA uint32_t*)(L + p.pver + ((uint32_t)q * 64 + lane) * 4) = 0u;
         if (lane < 8) *(LA uint32_t*)(L + p.pst + lane * 4) = 0u;
-        if constexpr (K::DUAL) { if (lane < 8) *(LA uint32_t*)(L + p.pst + (16 + lane) * 4) = 0u; }  // (the jobs' done marks)
         // Every centroid of the leaf-parent all-zero (sparse fingerprints under large branching factors): every similarity is 0 and
         // np.argmax returns row 0 (bitbirch.py:320) - no compare, and wave 2 is free to pre-compare for the leaf engine.  The
         // run ends with the insertion that makes row 0's centroid non-zero.
@@ -1335,19 +1249,8 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
         lds_st(L, p.ctl + PC_PGO * 4, 1u);
         uint32_t tail_seen = 0;
         auto retire_to_tail = [&]() {
-            // (two leaf engines finish their jobs out of order: each marks its job done, this wave retires them in order and
-            // publishes the tail for wave 2)
-            uint32_t t;
-            if constexpr (K::DUAL) {
-                t = retired;
-                while (t - retired < (uint32_t)K::PW && uni(lds_ld(L, p.pst + (16 + (t & (K::PW - 1))) * 4)) == t + 1) t += 1;
-            } else {
-                t = tail_seen;  // (read together with the abort flag at the top of the loop, or just now)
-            }
+            const uint32_t t = tail_seen;  // (read together with the abort flag at the top of the loop, or just now)
             PIPE_CBAR();
-            if constexpr (K::DUAL) {
-                if (t != retired) lds_st(L, p.ctl + PC_TAIL * 4, t);
-            }
             while (retired < t) {
                 const uint32_t jj = retired & (K::PW - 1);
                 const uint32_t prw = lds_ld(L, p.ring + jj * 16 + 8), apw = lds_ld(L, p.res + jj * 4);  // (both on their way, then both waited for)
@@ -1368,7 +1271,7 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
             }
         };
         auto retire_poll = [&]() {
-            if constexpr (!K::DUAL) tail_seen = uni(lds_ld(L, p.ctl + PC_TAIL * 4));
+            tail_seen = uni(lds_ld(L, p.ctl + PC_TAIL * 4));
             retire_to_tail();
         };
 #pragma unroll 1
@@ -1467,7 +1370,7 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
                     *pe = *pe + 1u;
                 }
                 u32x4_t job;
-                job.x = (uint32_t)e; job.y = leaf; job.z = j | (full ? 0x80000000u : 0u) | (K::DUAL ? (leaf & 1u) << 30 : 0u); job.w = pop;
+                job.x = (uint32_t)e; job.y = leaf; job.z = j | (full ? 0x80000000u : 0u); job.w = pop;
                 *(LA u32x4_t*)(L + p.ring + (issued & (K::PW - 1)) * 16) = job;
             }
             issued += 1;
@@ -1611,7 +1514,6 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
                 }
                 stg<uint32_t>(g_card + prow, cardn);
                 stg<uint32_t>((uint8_t*)(g_rm + prow) + 4, nnew);
-                stg<uint32_t>((uint8_t*)(g_rm + prow) + 12, 0u);  // flip distance of the batch mode: stale
             }
             e += 1;
             pph<PROF>(pr, 3);
@@ -1622,12 +1524,7 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
         {
             uint32_t spins = 0;
             while (true) {
-                if constexpr (K::DUAL) {
-                    retire_poll();
-                    if (retired == issued) break;
-                } else {
-                    if (uni(lds_ld(L, p.ctl + PC_TAIL * 4)) == issued) break;
-                }
+                if (uni(lds_ld(L, p.ctl + PC_TAIL * 4)) == issued) break;
                 __builtin_amdgcn_s_sleep(1);
                 if (uni(lds_ld(L, p.ctl + PC_ABORT * 4)) != 0u) { reason = PR_ABORT; break; }
                 if (++spins > PIPE_SPIN_LIMIT) { (PIPE_MARK(), lds_st(L, p.ctl + PC_ABORT * 4, (uint32_t)__LINE__)); reason = PR_ABORT; break; }
@@ -1745,15 +1642,7 @@ __device__ __forceinline__ void pipe_router_ml(LA unsigned char* L, TreeDev* T, 
     uint32_t dp[PNP];
 #pragma unroll
     for (int k = 0; k < PNP; ++k) dp[k] = 0;
-    constexpr int NTC = p.ntc;
-    static_assert(NTC >= 1, "the tracking cluster features go through the LDS cache");
-    uint32_t ttag[NTC], tuse[NTC];  // (keyed by the row's cf32 slot word)
-#pragma unroll
-    for (int c = 0; c < NTC; ++c) { ttag[c] = NONE; tuse[c] = 0; }
-    uint32_t tclock = 0;
-    (void)ttag; (void)tuse; (void)tclock;
-    // (K::CMT) requests posted to the helper waves, the levels of the last one, the levels of it known to be in the slots
-    constexpr bool CMT = K::CMT;
+    // requests posted to the helper waves, the levels of the last one, the levels of it known to be in the slots
     uint32_t cposted = 0, cn_last = 0, cseen = 0;
     bool lost_c = false;
     u64 rw[4] = {0, 0, 0, 0};  // (phase-timer build) what the router waits for, as in pipe_router
@@ -1761,34 +1650,30 @@ __device__ __forceinline__ void pipe_router_ml(LA unsigned char* L, TreeDev* T, 
     u64 cw_cycles = 0, cwa_cycles = 0;  // (phase-timer build) waiting for a level's update / for every update and its stores
     (void)cw_cycles; (void)cwa_cycles;
     auto commit_wait = [&](uint32_t l) {
-        if constexpr (CMT) {
-            if (cposted != 0u && l < cn_last && ((cseen >> l) & 1u) == 0u) {
-                const u64 t0_ = PROF ? __builtin_amdgcn_s_memtime() : 0;
-                const uint32_t need = (cposted - 1u) * 8u + (l >> 1) + 1u, off = p.mb + (CQ_PROG + (l & 1u)) * 4;
-                uint32_t spins = 0;
-                while ((int)(uni(lds_ld(L, off)) - need) < 0) {
-                    if (uni(lds_ld(L, p.ctl + PC_ABORT * 4)) != 0u || ++spins > PIPE_SPIN_LIMIT) { lost_c = true; PIPE_MARK(); break; }
-                }
-                PIPE_CBAR();
-                cseen |= 1u << l;
-                if constexpr (PROF) cw_cycles += __builtin_amdgcn_s_memtime() - t0_;
+        if (cposted != 0u && l < cn_last && ((cseen >> l) & 1u) == 0u) {
+            const u64 t0_ = PROF ? __builtin_amdgcn_s_memtime() : 0;
+            const uint32_t need = (cposted - 1u) * 8u + (l >> 1) + 1u, off = p.mb + (CQ_PROG + (l & 1u)) * 4;
+            uint32_t spins = 0;
+            while ((int)(uni(lds_ld(L, off)) - need) < 0) {
+                if (uni(lds_ld(L, p.ctl + PC_ABORT * 4)) != 0u || ++spins > PIPE_SPIN_LIMIT) { lost_c = true; PIPE_MARK(); break; }
             }
+            PIPE_CBAR();
+            cseen |= 1u << l;
+            if constexpr (PROF) cw_cycles += __builtin_amdgcn_s_memtime() - t0_;
         }
     };
     auto commit_wait_all = [&]() {
-        if constexpr (CMT) {
-            const u64 t0_ = PROF ? __builtin_amdgcn_s_memtime() : 0;
+        const u64 t0_ = PROF ? __builtin_amdgcn_s_memtime() : 0;
 #pragma unroll
-            for (uint32_t w = 0; w < 2; ++w) {
-                uint32_t spins = 0;
-                while (uni(lds_ld(L, p.mb + (CQ_FIN + w) * 4)) != cposted) {
-                    if (uni(lds_ld(L, p.ctl + PC_ABORT * 4)) != 0u || ++spins > PIPE_SPIN_LIMIT) { lost_c = true; PIPE_MARK(); break; }
-                }
+        for (uint32_t w = 0; w < 2; ++w) {
+            uint32_t spins = 0;
+            while (uni(lds_ld(L, p.mb + (CQ_FIN + w) * 4)) != cposted) {
+                if (uni(lds_ld(L, p.ctl + PC_ABORT * 4)) != 0u || ++spins > PIPE_SPIN_LIMIT) { lost_c = true; PIPE_MARK(); break; }
             }
-            PIPE_CBAR();
-            cseen = 0xFFu;
-            if constexpr (PROF) cwa_cycles += __builtin_amdgcn_s_memtime() - t0_;
         }
+        PIPE_CBAR();
+        cseen = 0xFFu;
+        if constexpr (PROF) cwa_cycles += __builtin_amdgcn_s_memtime() - t0_;
     };
     // the upper slots: lane s of these registers describes slot s (node, length, last use)
     uint32_t utag = NONE, ulen = 0, uuse = 0, uclock = 0;
@@ -1856,10 +1741,8 @@ __device__ __forceinline__ void pipe_router_ml(LA unsigned char* L, TreeDev* T, 
         const size_t pm = (size_t)nd * NG;
         bool early = true;
         const u64 ftin = PROF ? __builtin_amdgcn_s_memtime() : 0;
-        if constexpr (CMT) {
-            if (midrun && cposted != 0u && l < cn_last) early = uni(lds_ld(L, p.upath + l * 32 + 16)) != nd;
-            if (midrun && !early) commit_wait_all();
-        }
+        if (midrun && cposted != 0u && l < cn_last) early = uni(lds_ld(L, p.upath + l * 32 + 16)) != nd;
+        if (midrun && !early) commit_wait_all();
         // (the watermark is sampled BEFORE the leaves' headers are requested: what it promises is then in what they return)
         uint32_t wm = 0;
         if (plevel && midrun) {
@@ -1893,7 +1776,7 @@ __device__ __forceinline__ void pipe_router_ml(LA unsigned char* L, TreeDev* T, 
             const u64 n_ = __builtin_amdgcn_s_memtime();
             fprof[0] += n_ - ft0;
         }
-        if constexpr (CMT) { if (midrun && early) commit_wait_all(); }
+        if (midrun && early) commit_wait_all();
         const u64 ft1 = PROF ? __builtin_amdgcn_s_memtime() : 0;
 #pragma unroll
         for (int u = 0; u < NIT; ++u) {
@@ -2164,94 +2047,18 @@ __device__ __forceinline__ void pipe_router_ml(LA unsigned char* L, TreeDev* T, 
                 used += 1;
             }
             if constexpr (PROF) levels += ncommit;
-            if constexpr (CMT) {
-                // every exact level's tracking row: by the helper waves (pipe_commit_try), this wave goes on
-                if (lane == 0) {
-                    u32x2_t rq;
-                    rq.x = ncommit; rq.y = xoff;
-                    *(LA u32x2_t*)(L + p.mb + CQ_N * 4) = rq;
-                }
-                cposted += 1;
-                cn_last = ncommit;
-                cseen = 0;
-                PIPE_CBAR();
-                lds_st(L, p.mb + CQ_SEQ * 4, cposted);
+            // every exact level's tracking row (closest_subcluster.update, bitbirch.py:352-357): by the helper waves
+            // (pipe_commit_try), this wave goes on
+            if (lane == 0) {
+                u32x2_t rq;
+                rq.x = ncommit; rq.y = xoff;
+                *(LA u32x2_t*)(L + p.mb + CQ_N * 4) = rq;
             }
-            // every exact level's tracking row (closest_subcluster.update, bitbirch.py:352-357): CF += element, new centroid
-#pragma unroll 1
-            for (uint32_t l = 0; l < (CMT ? 0u : ncommit); ++l) {
-                const u32x4_t a = *(LA u32x4_t*)(L + p.upath + l * 32);
-                const uint32_t sb = uni(a.x), jl = uni(a.y), tl = uni(a.z), nl = uni(a.w);
-                const uint32_t ndl = uni(*(LA uint32_t*)(L + p.upath + l * 32 + 16));
-                const uint32_t nnew = nl + 1;
-                uint32_t k = NONE;
-#pragma unroll
-                for (int c = 0; c < NTC; ++c)
-                    if (ttag[c] == tl) k = (uint32_t)c;
-                uint32_t cf[32];
-                if (k == NONE) {
-                    if constexpr (PROF) tcf_miss += 1;
-                    uint32_t best = 0xFFFFFFFFu;
-#pragma unroll
-                    for (int c = 0; c < NTC; ++c)
-                        if (tuse[c] < best) { best = tuse[c]; k = (uint32_t)c; }
-                    uint32_t oldtag = NONE;
-#pragma unroll
-                    for (int c = 0; c < NTC; ++c)
-                        if (k == (uint32_t)c) { oldtag = ttag[c]; ttag[c] = tl; }
-                    if (oldtag != NONE) {
-                        uint32_t* dst = g_cf32 + (size_t)(oldtag & 0x3FFFFFFFu) * 2048 + (size_t)lane * 32;
-#pragma unroll
-                        for (int g = 0; g < 8; ++g) stg<u32x4_t>(dst + g * 4, *(LA u32x4_t*)(L + p.tcf + k * 8192 + ((uint32_t)g * 64 + lane) * 16));
-                    }
-                    const uint32_t* src = g_cf32 + (size_t)(tl & 0x3FFFFFFFu) * 2048 + (size_t)lane * 32;
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        const u32x4_t q = ldg<u32x4_t>(src + g * 4);
-                        cf[4 * g] = q.x; cf[4 * g + 1] = q.y; cf[4 * g + 2] = q.z; cf[4 * g + 3] = q.w;
-                    }
-                } else {
-#pragma unroll
-                    for (int g = 0; g < 8; ++g) {
-                        const u32x4_t q = *(LA u32x4_t*)(L + p.tcf + k * 8192 + ((uint32_t)g * 64 + lane) * 16);
-                        cf[4 * g] = q.x; cf[4 * g + 1] = q.y; cf[4 * g + 2] = q.z; cf[4 * g + 3] = q.w;
-                    }
-                }
-                tclock += 1;
-#pragma unroll
-                for (int c = 0; c < NTC; ++c)
-                    if (k == (uint32_t)c) tuse[c] = tclock;
-#pragma unroll
-                for (int i = 0; i < 32; ++i) cf[i] += xbit(xd, i);
-                const uint32_t cw = centroid_dword31(cf, nnew);
-#pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    u32x4_t q;
-                    q.x = cf[4 * g]; q.y = cf[4 * g + 1]; q.z = cf[4 * g + 2]; q.w = cf[4 * g + 3];
-                    *(LA u32x4_t*)(L + p.tcf + k * 8192 + ((uint32_t)g * 64 + lane) * 16) = q;
-                }
-                const uint32_t cardn = wsum32((uint32_t)__popc(cw));
-                const size_t prow = (size_t)ndl * NG + jl;
-                if (l == 0) {
-                    // (slot 0 is read by wave 2: the row's version is odd while it is being rewritten)
-                    const uint32_t pv = uni(lds_ld(L, p.pver + jl * 4));
-                    if (lane == 0) lds_st(L, p.pver + jl * 4, pv + 1);
-                    PIPE_CBAR();
-                    *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4) = cw;
-                    PIPE_CBAR();
-                    if (lane == 0) lds_st(L, p.pver + jl * 4, pv + 2);
-                } else {
-                    *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4) = cw;
-                }
-                stg<uint32_t>(g_cent + prow * 256 + lane * 4, cw);
-                if (lane == 0) {
-                    *(LA uint32_t*)(L + sb + p.p_card + jl * 4) = cardn;
-                    *(LA uint32_t*)(L + sb + p.p_n + jl * 4) = nnew;
-                    stg<uint32_t>(g_card + prow, cardn);
-                    stg<uint32_t>((uint8_t*)(g_rm + prow) + 4, nnew);
-                    stg<uint32_t>((uint8_t*)(g_rm + prow) + 12, 0u);  // flip distance of the batch mode: stale
-                }
-            }
+            cposted += 1;
+            cn_last = ncommit;
+            cseen = 0;
+            PIPE_CBAR();
+            lds_st(L, p.mb + CQ_SEQ * 4, cposted);
             e += 1;
             pph<PROF>(pr, 3);
             if (reason == PR_SPLIT) break;
@@ -2282,14 +2089,6 @@ __device__ __forceinline__ void pipe_router_ml(LA unsigned char* L, TreeDev* T, 
                     const bool leafparent = (uni(audit_ld((const uint8_t*)(T->node_hdr + uni(*(LA volatile uint32_t*)(L + p.pslot + si * p.pslot_bytes + p.p_link))) + 4)) & HW_LEAF) != 0u;
                     pipe_audit_tracking_slot<K>(L, T, p.pslot + si * p.pslot_bytes, nd_a, len_a, leafparent && reason != PR_SPLIT);
                 }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < (CMT ? 0 : NTC); ++c) {
-            if (ttag[c] != NONE) {
-                uint32_t* dst = g_cf32 + (size_t)(ttag[c] & 0x3FFFFFFFu) * 2048 + (size_t)lane * 32;
-#pragma unroll
-                for (int g = 0; g < 8; ++g) stg<u32x4_t>(dst + g * 4, *(LA u32x4_t*)(L + p.tcf + (uint32_t)c * 8192 + ((uint32_t)g * 64 + lane) * 16));
             }
         }
 #pragma unroll
@@ -2330,7 +2129,7 @@ __device__ __forceinline__ void pipe_router_ml(LA unsigned char* L, TreeDev* T, 
 // SH: wave 3 shares this wave's compares and fills (nodes of > 64 rows whose leaf-parent is not all-zero); a compile-time
 // parameter - the two variants of the loop share little, and each is shorter and needs fewer live scalars without the other
 template <class K, bool PROF, bool SH>
-__device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint32_t eng = 0) {
+__device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
     PProf pr;
     pph_init<PROF>(pr);
     constexpr PSmem p = K::p;
@@ -2351,34 +2150,15 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
     const int tol_len = (int)uni((uint32_t)T->tol_len);
     constexpr int crit = K::CRIT;
     LA uint32_t* lctr = (LA uint32_t*)(L + p.ctr);
-    // (K::DUAL: the counters stay in LDS, shared by the two engines - ids under the ticket, pool slots through atomics)
-    constexpr bool DUAL = K::DUAL;
     uint32_t cI = uni(lctr[C_IDS]), c8 = uni(lctr[C_N8]), c16 = uni(lctr[C_N16]), c32 = uni(lctr[C_N32]);
-    (void)cI; (void)c8; (void)c16; (void)c32;
-    auto take8 = [&]() -> uint32_t {
-        if constexpr (DUAL) { uint32_t v = 0; if (lane == 0) v = __hip_atomic_fetch_add(lctr + C_N8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); return uni(v); }
-        else return c8++;
-    };
-    auto take16 = [&]() -> uint32_t {
-        if constexpr (DUAL) { uint32_t v = 0; if (lane == 0) v = __hip_atomic_fetch_add(lctr + C_N16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); return uni(v); }
-        else return c16++;
-    };
-    auto take32 = [&]() -> uint32_t {
-        if constexpr (DUAL) { uint32_t v = 0; if (lane == 0) v = __hip_atomic_fetch_add(lctr + C_N32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); return uni(v); }
-        else return c32++;
-    };
     uint32_t st_merge = 0, st_append = 0, st_calls = 0, st_rows = 0, st_stale = 0;
     // which leaf sits in which slot, and its length: lane s of two vector registers (as scalars they were a dozen of the
     // loop's live SGPRs, and the compiler parked other scalars in vector lanes around them)
     uint32_t tagv = NONE, slenv = 0;
     constexpr int NCF = p.ncf;
-    // this engine's leaf slots [sl0, sl0 + NLE) and cache entries [cf0, cf0 + NCFE)
-    constexpr int NLE = DUAL ? NL / 2 : NL, NCFE = DUAL ? NCF / 2 : NCF;
-    static_assert(!DUAL || (NLE >= 1 && NCFE >= 1), "two leaf engines: at least one leaf slot and one cache entry each");
-    const uint32_t sl0 = DUAL ? eng * (uint32_t)NLE : 0u, cf0 = DUAL ? eng * (uint32_t)NCFE : 0u;
     uint32_t ctagv = NONE;  // tags of the cluster-feature cache: lane c
-    uint32_t cvict = cf0;
-    uint32_t victim = sl0;
+    uint32_t cvict = 0;
+    uint32_t victim = 0;
     uint32_t j = 0;
     uint32_t hseq = 0;
     constexpr uint32_t MB = p.mb + 32, PART = p.part + (uint32_t)(RPL * 256), ABO = p.ctl + PC_ABORT * 4;
@@ -2388,33 +2168,16 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
     constexpr bool shared = SH;
     static_assert(!SH || RPL > 1, "sharing is for nodes of several rows per lane");
     constexpr uint32_t LANES4 = (uint32_t)RPL * 256;
-    constexpr bool ASYNC_L = K::ASYNC_L;
-    if constexpr (ASYNC_L) {
-        // row versions, published slot tags / lengths and stamps start from zero, then wave 3 may go
+    // row versions, published slot tags / lengths and stamps start from zero, then wave 3 may go
 #pragma unroll
-        for (int sl = 0; sl < NL; ++sl)
+    for (int sl = 0; sl < NL; ++sl)
 #pragma unroll
-            for (int q = 0; q < RPL; ++q) *(LA uint32_t*)(L + p.lver + (uint32_t)sl * LANES4 + ((uint32_t)q * 64 + lane) * 4) = 0u;
-        if (lane < 4) *(LA uint32_t*)(L + p.pst + (8 + lane) * 4) = 0u;
-        if (lane < 8) { *(LA uint32_t*)(L + p.pst + (16 + lane) * 4) = NONE; *(LA uint32_t*)(L + p.pst + (24 + lane) * 4) = 0u; }
-        if constexpr (RPL > 1) { if (lane < (uint32_t)NL) *(LA uint32_t*)(L + p.llog + lane * 64) = 0u; }
-        if constexpr (!DUAL && PIPE_KEEP_LEAF<K::BF>) {
-            // leaf slot 0 as the run before left it (PST_KEEP): rows, popcounts, slot words and records are in place
-            const uint32_t kl = uni(lds_ld(L, p.pst + PST_KEEP * 4)), klen = uni(lds_ld(L, p.pst + (PST_KEEP + 1) * 4));
-            if (kl != NONE) {
-                tagv = lane == 0 ? kl : tagv;
-                slenv = lane == 0 ? klen : slenv;
-                if (NLE > 1) victim = sl0 + 1;
-                PIPE_CBAR();
-                if (lane == 0) {
-                    *(LA uint32_t*)(L + p.pst + 24 * 4) = klen;
-                    *(LA uint32_t*)(L + p.pst + 16 * 4) = kl;
-                }
-            }
-        }
-        PIPE_CBAR();
-        lds_st(L, p.ctl + PC_LGO * 4, 1u);
-    }
+        for (int q = 0; q < RPL; ++q) *(LA uint32_t*)(L + p.lver + (uint32_t)sl * LANES4 + ((uint32_t)q * 64 + lane) * 4) = 0u;
+    if (lane < 4) *(LA uint32_t*)(L + p.pst + (8 + lane) * 4) = 0u;
+    if (lane < 8) { *(LA uint32_t*)(L + p.pst + (16 + lane) * 4) = NONE; *(LA uint32_t*)(L + p.pst + (24 + lane) * 4) = 0u; }
+    if constexpr (RPL > 1) { if (lane < (uint32_t)NL) *(LA uint32_t*)(L + p.llog + lane * 64) = 0u; }
+    PIPE_CBAR();
+    lds_st(L, p.ctl + PC_LGO * 4, 1u);
     (void)tolerance;
 #pragma unroll 1
     while (true) {
@@ -2423,26 +2186,9 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
             uint32_t spins = 0;
             bool stop = false;
             while (true) {
-                if constexpr (DUAL) {
-                    // (jobs below the router's tail are all done - none of them is this engine's next one - and their ring
-                    // entries may have been handed out again: the cursor never reads behind the tail)
-                    const uint32_t t = uni(lds_ld(L, p.ctl + PC_TAIL * 4));
-                    if (j < t) { j = t; spins = 0; }
-                }
                 const uint32_t h = uni(lds_ld(L, p.ctl + PC_HEAD * 4));
                 if (h != j) {
                     PIPE_CBAR();
-                    if constexpr (DUAL) {
-                        // the other engine's jobs are passed over (jobs of one leaf all go to one engine, in order).  The entry
-                        // is only trusted if the tail has not passed it meanwhile: the router publishes the tail before it
-                        // reuses an entry, and a job of this engine cannot retire before this engine has done it.
-                        const uint32_t z = uni(lds_ld(L, p.ring + (j & (K::PW - 1)) * 16 + 8));
-                        PIPE_CBAR();
-                        if (uni(lds_ld(L, p.ctl + PC_TAIL * 4)) > j) continue;
-                        // (the bound on this wait is about a pipeline that has stopped moving, not about an engine without
-                        // work: a stream that keeps going to the other engine's leaves - a run of duplicates - is progress)
-                        if (((z >> 30) & 1u) != eng) { j += 1; spins = 0; continue; }
-                    }
                     break;
                 }
                 if (uni(lds_ld(L, p.ctl + PC_END * 4)) != 0u) {
@@ -2470,23 +2216,19 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
         bool filled = false;
         if (si == NONE) {
             si = victim;
-            victim = victim + 1 == sl0 + (uint32_t)NLE ? sl0 : victim + 1;
+            victim = victim + 1 == (uint32_t)NL ? 0u : victim + 1;
             const uint32_t sb = si == 0 ? p.leaf0 : p.lrest + (si - 1) * p.lslot_bytes;
             const size_t lm = (size_t)leaf * NG;
             const uint32_t hl = ldg<uint32_t>(g_hdr + leaf);
             uint32_t fv[RPL];
+            // the slot changes hands: no tag while it is filled, every row's version odd, then a new even value
+            if (lane == 0) lds_st(L, p.pst + (16 + si) * 4, NONE);
 #pragma unroll
-            for (int q = 0; q < RPL; ++q) fv[q] = 0;
-            if constexpr (ASYNC_L) {
-                // the slot changes hands: no tag while it is filled, every row's version odd, then a new even value
-                if (lane == 0) lds_st(L, p.pst + (16 + si) * 4, NONE);
-#pragma unroll
-                for (int q = 0; q < RPL; ++q) {
-                    fv[q] = lds_ld(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4) | 1u;
-                    lds_st(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4, fv[q]);
-                }
-                PIPE_CBAR();
+            for (int q = 0; q < RPL; ++q) {
+                fv[q] = lds_ld(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4) | 1u;
+                lds_st(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4, fv[q]);
             }
+            PIPE_CBAR();
             // (the helper reads what this wave wrote through when the leaf last sat in a slot: those stores have to be done)
             // (bringing in only the rows the leaf can have - the router knows an upper bound - was tried: run-time chunk
             // bounds cost the fill more than the 25 % of the bytes they save)
@@ -2516,17 +2258,15 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
             tagv = lane == si ? leaf : tagv;
             slenv = lane == si ? hlen : slenv;
             if (shared && !pipe_wait_helper(L, MB, hseq, ABO)) { helper_lost = true; break; }
-            if constexpr (ASYNC_L) {
-                PIPE_CBAR();
+            PIPE_CBAR();
 #pragma unroll
-                for (int q = 0; q < RPL; ++q) lds_st(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4, fv[q] + 1u);
-                if (lane == 0) {
-                    // (what was pre-compared against the slot's previous rows is out of the log's reach)
-                    if constexpr (RPL > 1) lds_st(L, p.llog + si * 64, lds_ld(L, p.llog + si * 64) + PLOGK + 1);
-                    lds_st(L, p.pst + (24 + si) * 4, hlen);
-                    PIPE_CBAR();
-                    lds_st(L, p.pst + (16 + si) * 4, leaf);
-                }
+            for (int q = 0; q < RPL; ++q) lds_st(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4, fv[q] + 1u);
+            if (lane == 0) {
+                // (what was pre-compared against the slot's previous rows is out of the log's reach)
+                if constexpr (RPL > 1) lds_st(L, p.llog + si * 64, lds_ld(L, p.llog + si * 64) + PLOGK + 1);
+                lds_st(L, p.pst + (24 + si) * 4, hlen);
+                PIPE_CBAR();
+                lds_st(L, p.pst + (16 + si) * 4, leaf);
             }
             filled = true;
             (void)filled;
@@ -2542,7 +2282,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
         uint32_t cnow = 0;
         if constexpr (!CHLOG) {
             bool pre = false;
-            if (ASYNC_L && !shared) {
+            if (!shared) {
                 const uint32_t stp = uni(lds_ld(L, p.pst + (8 + (j & (K::PREWL - 1))) * 4));
                 pre = stp == ((j + 1) | (si << 28));
                 PIPE_CBAR();
@@ -2623,12 +2363,10 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
         }
         st_calls += 1;
         st_rows += len;
-#ifndef BBH_DET_CF
         if constexpr (PROF) {
             det[2 * cls] += __builtin_amdgcn_s_memtime() - pr.mark;
             det[2 * cls + 1] += 1;
         }
-#endif
         pph<PROF>(pr, 7);
         const u32x4_t ma = *(LA u32x4_t*)(L + sb + p.s_rm + jl * 32);
         const u32x4_t mb = *(LA u32x4_t*)(L + sb + p.s_rm + jl * 32 + 16);
@@ -2722,13 +2460,6 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
                 for (int u = 0; u < 8; ++u) d32 = __builtin_amdgcn_sad_u8(w[u] & ((xs[u] << 8) - xs[u]), 0u, d32);  // (0x01 -> 0xFF per byte)
                 dot = wsum32(d32);
             }
-#ifdef BBH_DET_CF
-            if constexpr (PROF) {
-                const int c3 = nT == 1 ? 0 : (chit != NONE ? 1 : 2);
-                det[2 * c3] += __builtin_amdgcn_s_memtime() - pr.mark;
-                det[2 * c3 + 1] += 1;
-            }
-#endif
             pph<PROF>(pr, 8);
             s2n = s2T + 2ull * dot + pop;
             accept = decide(dot);
@@ -2737,7 +2468,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
                 if (nT == 1) {
                     // two members: a feature is in the centroid if either has it (2 ls >= 2), no majority vote to take;
                     // the BitFeature gets its uint8 row now (SLOT_LAZY8)
-                    slotN = take8();
+                    slotN = c8++;
 #pragma unroll
                     for (int u = 0; u < 8; ++u) w[u] += xs[u];
                     cw = *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4) | xd;
@@ -2764,7 +2495,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
                 if constexpr (NCF > 0) {
                     if (chit == NONE) {  // first in, first out
                         chit = cvict;
-                        cvict = cvict + 1 == cf0 + (uint32_t)NCFE ? cf0 : cvict + 1;
+                        cvict = cvict + 1 == (uint32_t)NCF ? 0u : cvict + 1;
                         ctagv = lane == chit ? slotN : ctagv;
                     }
                     *(LA u32x4_t*)(L + p.cfc + chit * 2048 + lane * 32) = q0;
@@ -2808,7 +2539,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
                 cw = centroid_dword31(v, (uint32_t)new_n);
                 const uint32_t ntier = tier_for(new_n) > tierT ? tier_for(new_n) : tierT;
                 if (ntier != tierT) {
-                    slotN = (ntier << 30) | (ntier == 1 ? take16() : take32());
+                    slotN = (ntier << 30) | (ntier == 1 ? c16++ : c32++);
                     resw |= 2u;
                 }
                 const size_t cfo = (size_t)(slotN & 0x3FFFFFFFu) * 2048 + (size_t)lane * 32;
@@ -2825,37 +2556,13 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
                 }
             }
         }
-        // Two engines: BitFeature ids are numbered in JOB order (bitbirch.py:284-287 numbers them in insertion order).  The decision
-        // itself depends on this job's leaf alone; the id of an appended BitFeature on how many of the jobs before it appended.
-        // PC_DEC = jobs decided so far: a job waits for its turn, takes the next id if it appends, and passes the ticket on.
-        uint32_t ticket_id = 0;
-        bool ticket_lost = false;
-        if constexpr (DUAL) {
-            uint32_t spins = 0;
-            while (uni(lds_ld(L, p.ctl + PC_DEC * 4)) != j) {
-                if (uni(lds_ld(L, p.ctl + PC_ABORT * 4)) != 0u || ++spins > PIPE_SPIN_LIMIT) { ticket_lost = true; PIPE_MARK(); break; }
-            }
-            PIPE_CBAR();
-            if (!ticket_lost) {
-                if (!accept) {
-                    ticket_id = uni(lctr[C_IDS]);
-                    if (lane == 0) lctr[C_IDS] = ticket_id + 1;
-                }
-                PIPE_CBAR();
-                lds_st(L, p.ctl + PC_DEC * 4, j + 1);
-            }
-        }
-        if (ticket_lost) { (PIPE_MARK(), lds_st(L, p.ctl + PC_ABORT * 4, (uint32_t)__LINE__)); break; }
         if (accept) {
             const uint32_t cardn = wsum32((uint32_t)__popc(cw));
-            uint32_t rv = 0;
-            if constexpr (ASYNC_L) {
-                rv = uni(lds_ld(L, p.lver + si * LANES4 + jl * 4));
-                if (lane == 0) lds_st(L, p.lver + si * LANES4 + jl * 4, rv + 1);
-                PIPE_CBAR();
-            }
+            const uint32_t rv = uni(lds_ld(L, p.lver + si * LANES4 + jl * 4));
+            if (lane == 0) lds_st(L, p.lver + si * LANES4 + jl * 4, rv + 1);
+            PIPE_CBAR();
             *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4) = cw;
-            if constexpr (ASYNC_L && CHLOG) {
+            if constexpr (CHLOG) {
                 // (the row's popcount belongs to the row: inside the version window; then the change is logged and counted)
                 if (lane == 0) {
                     *(LA uint32_t*)(L + sb + p.s_card + jl * 4) = cardn;
@@ -2865,7 +2572,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
                     PIPE_CBAR();
                     lds_st(L, p.llog + si * 64, cnow + 1);
                 }
-            } else if constexpr (ASYNC_L) {
+            } else {
                 PIPE_CBAR();
                 if (lane == 0) lds_st(L, p.lver + si * LANES4 + jl * 4, rv + 2);
             }
@@ -2889,17 +2596,14 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
             out_id = Tsub;
         } else {
             // append_subcluster (bitbirch.py:284-287): a new leaf BitFeature in the next row (the router made sure it fits)
-            const uint32_t s = DUAL ? ticket_id : cI++;
+            const uint32_t s = cI++;
             const uint32_t slotw = SLOT_LAZY8;  // no uint8 slot: one fingerprint's cluster features are its centroid row
             const size_t m = lm + len;
-            uint32_t rv = 0;
-            if constexpr (ASYNC_L) {
-                rv = uni(lds_ld(L, p.lver + si * LANES4 + len * 4));
-                if (lane == 0) lds_st(L, p.lver + si * LANES4 + len * 4, rv + 1);
-                PIPE_CBAR();
-            }
+            const uint32_t rv = uni(lds_ld(L, p.lver + si * LANES4 + len * 4));
+            if (lane == 0) lds_st(L, p.lver + si * LANES4 + len * 4, rv + 1);
+            PIPE_CBAR();
             *(LA uint32_t*)(L + sb + __umul24(len, FRBS) + lane * 4) = xd;
-            if constexpr (ASYNC_L && CHLOG) {
+            if constexpr (CHLOG) {
                 if (lane == 0) {
                     *(LA uint32_t*)(L + sb + p.s_card + len * 4) = pop;
                     PIPE_CBAR();
@@ -2909,7 +2613,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
                     PIPE_CBAR();
                     lds_st(L, p.llog + si * 64, cnow + 1);
                 }
-            } else if constexpr (ASYNC_L) {
+            } else {
                 PIPE_CBAR();
                 if (lane == 0) {
                     lds_st(L, p.lver + si * LANES4 + len * 4, rv + 2);
@@ -2942,8 +2646,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
         lds_st(L, p.res + (j & (K::PW - 1)) * 4, resw);
         j += 1;
         PIPE_CBAR();
-        if constexpr (DUAL) lds_st(L, p.pst + (16 + ((j - 1) & (K::PW - 1))) * 4, j);  // done: the router retires the jobs in order
-        else lds_st(L, p.ctl + PC_TAIL * 4, j);
+        lds_st(L, p.ctl + PC_TAIL * 4, j);
         pph<PROF>(pr, 9);
     }
     pph<PROF>(pr, 5);
@@ -2983,17 +2686,8 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T, uint3
         }
     }
     if constexpr (SH) pipe_post(L, MB, hseq, PO_EXIT, 0, 0, 0);  // (wave 3 in its sharing role)
-    if constexpr (!DUAL && ASYNC_L && PIPE_KEEP_LEAF<K::BF>) {
-        // what leaf slot 0 holds goes on to the next run (every change was written through: slot and HBM agree)
-        const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)tagv, 0), l0 = (uint32_t)__builtin_amdgcn_readlane((int)slenv, 0);
-        const bool good = !helper_lost && uni(lds_ld(L, p.ctl + PC_ABORT * 4)) == 0u;
-        if (lane == 0) {
-            *(LA uint32_t*)(L + p.pst + PST_KEEP * 4) = good ? t0 : NONE;
-            *(LA uint32_t*)(L + p.pst + (PST_KEEP + 1) * 4) = l0;
-        }
-    }
     if (lane == 0) {
-        if constexpr (!DUAL) { lctr[C_IDS] = cI; lctr[C_N8] = c8; lctr[C_N16] = c16; lctr[C_N32] = c32; }
+        lctr[C_IDS] = cI; lctr[C_N8] = c8; lctr[C_N16] = c16; lctr[C_N32] = c32;
         LA u64* lstats = (LA u64*)(L + p.stats);
         __hip_atomic_fetch_add(lstats + 0, (u64)st_calls, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_add(lstats + 1, (u64)st_rows, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -3052,7 +2746,6 @@ __device__ __forceinline__ void tree_pipe_body(unsigned char* smem_raw, TreeDev*
     if (tid < 8) lstats[tid] = T->stats[tid];
     if (tid < 16) ((LA u32x4_t*)(L + p.x))[tid] = (u32x4_t)(0);
     if (tid < PZ * 8) ((LA uint32_t*)(L + p.zrec))[tid] = NONE;
-    if (tid == 0) *(LA uint32_t*)(L + p.pst + PST_KEEP * 4) = NONE;
     __syncthreads();
     const long long n_elems = T->n_elems;
     long long e = 0;
@@ -3084,8 +2777,7 @@ __device__ __forceinline__ void tree_pipe_body(unsigned char* smem_raw, TreeDev*
             }
         }
         else if (wave == 2) pipe_prep<K>(L, T, e);
-        else if (K::DUAL) pipe_leaf<K, PROF, false>(L, T, 1u);
-        else if (K::CMT) pipe_prel_cmt<K>(L, T);
+        else if (K::ML) pipe_prel_cmt<K>(L, T);
         else if (K::RPL == 1) pipe_prel<K>(L, 0u, 1u);
         else {
             // nodes of > 64 rows: wave 3 shares the leaf engine's compares and fills - unless the leaf-parent is all-zero, when
@@ -3149,7 +2841,6 @@ __device__ __forceinline__ void tree_pipe_body(unsigned char* smem_raw, TreeDev*
         // (the complete engine may have split a node of the zero levels: the row that tracks the split node keeps its cf32 slot
         // (split_node) with another node's sums in it - the cached flip distances, keyed by node and slot, start over)
         if (tid < PZ * 8) ((LA uint32_t*)(L + p.zrec))[tid] = NONE;
-        if (tid == 0) *(LA uint32_t*)(L + p.pst + PST_KEEP * 4) = NONE;  // (... or inserted into the leaf that sits in leaf slot 0)
         __syncthreads();
         if constexpr (PROF) { if (tid == 0) T->phase[11] += __builtin_amdgcn_s_memtime() - c1; }
         if (cstop != STOP_DONE || cdone == 0) { stop = (int)cstop; break; }

@@ -356,7 +356,6 @@ __device__ __forceinline__ void sys_commit(const KCt& k, SysCtx<KCt>& c, const E
     if (n_new > 0xFFFFFFFFull) sys_abort(c, __LINE__);
     if (tid == 0) {
         stg<uint32_t>((uint8_t*)(k.rm + pm) + 4, (uint32_t)n_new);
-        stg<uint32_t>((uint8_t*)(k.rm + pm) + 12, 0u);  // flip distance now stale
         stg<uint32_t>(k.card + pm, (uint32_t)cc[0]);
         lds<uint32_t>(k.L, k.o.rc_card)[(uint32_t)ms * k.rows + j] = (uint32_t)cc[0];
         c.sl[SL_FIXED + ((uint32_t)ms * k.rows + j) * RS_WORDS + RS_N] = (uint32_t)n_new;

@@ -207,8 +207,7 @@ def multiround_shard(case: dict, seed: int, make_fake) -> np.ndarray:
 def clustered_dense(n: int, n_features: int, k: int, seed: int, flip: float = 0.08) -> np.ndarray:
     r"""k dense prototypes (45-60 % bits set), every row = a random prototype with `flip` of its
     bits toggled, in random order.  Unlike S-fake / S-ecfp the majority centroids of the upper tree
-    levels stay informative, so consecutive fingerprints are routed to DIFFERENT subtrees - the
-    workload that exercises concurrent gates in batch mode."""
+    levels stay informative, so consecutive fingerprints are routed to DIFFERENT subtrees."""
     rng = np.random.default_rng(seed)
     dens = rng.uniform(0.45, 0.60, k)
     protos = rng.random((k, n_features)) < dens[:, None]

@@ -119,22 +119,3 @@ def test_gc_sealed_leaves_give_their_rows_back():
     assert (hip.get_assignments() == plain.get_assignments()).all()
     assert used < 0.35 * used_plain, (used, used_plain)
     assert used < 700 * n, f"{used / n:.0f} bytes of node rows per fingerprint"
-
-
-def test_gc_batch_mode_thaws_everything_first():
-    r"""The exact batch mode (concurrent gates, BBHIP_BATCH=1) never moves a node: a tree with sealed nodes is brought back to
-    full capacity before its first batch."""
-    rng = np.random.default_rng(9400)
-    rows = np.concatenate([_segment(rng, 12_000, 1), _segment(rng, 8_000, 2)])
-    kw = dict(branching_factor=50, threshold=0.6, merge_criterion="diameter")
-    hip, ora = BitBirch(**kw), BitBirch(_engine_factory=OracleEngine, **kw)
-    hip.fit(rows[:10_000])
-    ora.fit(rows[:10_000])
-    hip._engine.compact(True)
-    hip._engine.compact(True)
-    assert int(hip._engine.memory()[5]) > 0
-    with _Env(BBHIP_BATCH="512"):
-        hip.fit(rows[10_000:])
-    ora.fit(rows[10_000:])
-    assert (hip._log_leaf[-1] == ora._log_leaf[-1]).all()
-    _same_tables(hip, ora)
