@@ -362,6 +362,21 @@ class HipEngine:
             )
         return out
 
+    def gather_centroids(self, positions: NDArray[np.int64], device_out: bool = False) -> object:
+        r"""Packed centroids of the leaves at `positions` (chain order); `device_out`: a ``torch.uint8`` tensor in HBM."""
+        pos = np.ascontiguousarray(positions, dtype=np.int64)
+        if device_out:
+            import torch
+
+            out_t = torch.empty((pos.size, self.nbytes), dtype=torch.uint8, device=torch.device("cuda", self.device))
+            if pos.size:
+                _lib.check(self._lib.bbh_tree_gather_centroids(self._h, pos.ctypes.data, pos.size, int(out_t.data_ptr())))
+            return out_t
+        out = np.empty((pos.size, self.nbytes), dtype=np.uint8)
+        if pos.size:
+            _lib.check(self._lib.bbh_tree_gather_centroids(self._h, pos.ctypes.data, pos.size, out.ctypes.data))
+        return out
+
     def stats(self) -> NDArray[np.uint64]:
         out = np.zeros(8, dtype=np.uint64)
         _lib.check(self._lib.bbh_tree_stats(self._h, out.ctypes.data))

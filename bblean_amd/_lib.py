@@ -38,6 +38,9 @@ _PROTOTYPES = {
     "bbh_popcount_rows": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "bbh_jt_arr_vec": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbh_jt_best_match": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "bbh_jt_assign": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "bbh_jt_dist_matrix": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
+    "bbh_mfma_i8_probe": (_int, [_vp, _vp, _vp, _vp]),
     "bbh_unpack": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "bbh_pack": (_int, [_vp, _i64, _i64, _vp, _vp]),
     "bbh_add_rows": (_int, [_vp, _i64, _i64, _int, _i64, _vp, _vp]),

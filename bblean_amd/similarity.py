@@ -13,6 +13,7 @@ Inputs may be NumPy arrays (staged to HBM for the call) or CUDA/HIP ``torch`` te
 from __future__ import annotations
 
 import ctypes as C
+import os
 import warnings
 
 import numpy as np
@@ -39,6 +40,8 @@ __all__ = [
     "jt_stratified_sampling",
     "jt_sim_matrix_packed",
     "jt_best_match_packed",
+    "jt_assign_packed",
+    "jt_dist_matrix_packed",
 ]
 
 
@@ -158,6 +161,103 @@ def jt_best_match_packed(
                               sims.ctypes.data if sims is not None else None, None)
     )
     return idx, inter, union, sims
+
+
+# ------------------------------------------------- assignment to fitted clusters ---
+def _slab_rows(row_bytes: int) -> int:
+    r"""Host rows staged per call: `BBHIP_SLAB_KB` (default 256 MiB) names the slab, as for the tree's input."""
+    kb = int(os.environ.get("BBHIP_SLAB_KB", str(256 * 1024)))
+    return max(1, (kb * 1024) // max(1, row_bytes))
+
+
+def _assign_operands(queries: object, centroids: object) -> tuple[object, int, int, int, object, int]:
+    q, nq, nb, q_stride = _u8_2d(queries, "queries")
+    if _is_dev(q) and str(q.dtype) != "torch.uint8":  # type: ignore[attr-defined]
+        raise RuntimeError("queries must be uint8")
+    if _is_dev(centroids):
+        c = centroids if centroids.is_contiguous() else centroids.contiguous()  # type: ignore[attr-defined]
+        if c.dim() != 2 or str(c.dtype) != "torch.uint8":  # type: ignore[attr-defined]
+            raise RuntimeError("centroids must be 2-dimensional uint8")
+        nc, nb2 = int(c.shape[0]), int(c.shape[1])  # type: ignore[attr-defined]
+    else:
+        c, nc, nb2, _ = _u8_2d(centroids, "centroids")
+    if nb != nb2:
+        raise RuntimeError("queries and centroids must have the same packed width")
+    if nc < 1:
+        raise RuntimeError("need at least one centroid row")
+    return q, nq, nb, q_stride, c, nc
+
+
+def jt_assign_packed(queries: object, centroids: object, return_counts: bool = False):  # type: ignore[no-untyped-def]
+    r"""Nearest centroid of every packed query row: the FIRST index of the minimum Jaccard distance
+    ``(u - i) / u`` (0 where ``u == 0``), i.e. `sklearn.metrics.pairwise_distances_argmin(..., metric="jaccard")`
+    as the reference's `BitBirch.predict` calls it (sklearn.py:136) - on packed rows, on the device.
+
+    Returns int32 indices; with ``return_counts`` also the winning pair's exact uint32 intersection and union.
+    Device tensors in -> device tensors out, on the current stream; host queries larger than a slab
+    (`BBHIP_SLAB_KB`) are staged slab by slab, so a memory-mapped file of any size can be assigned."""
+    lib = _lib.load()
+    q, nq, nb, q_stride, c, nc = _assign_operands(queries, centroids)
+    if _is_dev(q):
+        import torch
+
+        dev = q.device  # type: ignore[attr-defined]
+        if not _is_dev(c):
+            c = torch.from_numpy(c).to(dev)
+        idx_t = torch.empty(nq, dtype=torch.int32, device=dev)
+        cnt_t = torch.empty((2, nq), dtype=torch.int32, device=dev) if return_counts else None
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.bbh_jt_assign(_lib.ptr(q), nq, q_stride, _lib.ptr(c), nc, nb, _lib.ptr(idx_t),
+                                     int(cnt_t[0].data_ptr()) if cnt_t is not None else None,
+                                     int(cnt_t[1].data_ptr()) if cnt_t is not None else None, st))
+        return (idx_t, cnt_t[0], cnt_t[1]) if cnt_t is not None else idx_t
+    idx = np.empty(nq, dtype=np.int32)
+    inter = np.empty(nq, dtype=np.uint32) if return_counts else None
+    union = np.empty(nq, dtype=np.uint32) if return_counts else None
+    slab = _slab_rows(nb)
+    cdev: object = c
+    if nq > slab and not _is_dev(c):  # several calls: the centroids are staged once
+        import torch
+
+        cdev = torch.from_numpy(c).cuda()
+    for lo in range(0, nq, slab):
+        hi = min(nq, lo + slab)
+        part = q[lo:hi]  # type: ignore[index]
+        _lib.check(lib.bbh_jt_assign(part.ctypes.data, hi - lo, q_stride, _lib.ptr(cdev), nc, nb,
+                                     idx[lo:hi].ctypes.data,
+                                     inter[lo:hi].ctypes.data if inter is not None else None,
+                                     union[lo:hi].ctypes.data if union is not None else None, None))
+    return (idx, inter, union) if return_counts else idx
+
+
+def jt_dist_matrix_packed(queries: object, centroids: object):  # type: ignore[no-untyped-def]
+    r"""The ``nq x nc`` float64 Jaccard distances ``(u - i) / u`` (one division of exact integers, 0.0 where
+    ``u == 0``): bit for bit `sklearn.metrics.pairwise_distances(..., metric="jaccard")` on the unpacked rows, which
+    is what the reference's `BitBirch.transform` returns (sklearn.py:153).  Device in -> device out."""
+    lib = _lib.load()
+    q, nq, nb, q_stride, c, nc = _assign_operands(queries, centroids)
+    if _is_dev(q):
+        import torch
+
+        dev = q.device  # type: ignore[attr-defined]
+        if not _is_dev(c):
+            c = torch.from_numpy(c).to(dev)
+        out_t = torch.empty((nq, nc), dtype=torch.float64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.bbh_jt_dist_matrix(_lib.ptr(q), nq, q_stride, _lib.ptr(c), nc, nb, _lib.ptr(out_t), st))
+        return out_t
+    out = np.empty((nq, nc), dtype=np.float64)
+    slab = _slab_rows(max(nb, nc * 8))
+    cdev = c
+    if nq > slab and not _is_dev(c):
+        import torch
+
+        cdev = torch.from_numpy(c).cuda()
+    for lo in range(0, nq, slab):
+        hi = min(nq, lo + slab)
+        _lib.check(lib.bbh_jt_dist_matrix(q[lo:hi].ctypes.data, hi - lo, q_stride, _lib.ptr(cdev), nc, nb,  # type: ignore[index]
+                                          out[lo:hi].ctypes.data, None))
+    return out
 
 
 def jt_sim_matrix_packed(arr: NDArray[np.uint8]) -> NDArray[np.float64]:

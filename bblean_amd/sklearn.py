@@ -1,0 +1,184 @@
+r"""`bblean.sklearn` on the MI355X engine: `BitBirch` / `UnpackedBitBirch` that respect the scikit-learn estimator
+contract (reference bblean/sklearn.py), with the caveat the reference has: no global clustering.
+
+Same constructor, mixin order, method signatures, fitted attributes and return dtypes as the reference classes.
+`fit` is the device tree of `bblean_amd.bitbirch.BitBirch`; `predict` and `transform` - which the reference
+computes on the CPU with `sklearn.metrics.pairwise_distances_argmin` / `pairwise_distances` on unpacked boolean
+arrays (sklearn.py:136, :153) - run as HIP kernels on the PACKED centroids, which stay in HBM after `fit`
+(`bblean_amd.similarity.jt_assign_packed`, `jt_dist_matrix_packed`).  The results are identical, ties and all-zero
+rows included.  There is no NumPy fallback.
+
+scikit-learn is imported by this module only; `import bblean_amd` works without it.
+"""
+from __future__ import annotations
+
+import typing as tp
+
+import numpy as np
+from numpy.typing import NDArray
+from sklearn.base import (
+    BaseEstimator,
+    ClassNamePrefixFeaturesOutMixin,
+    ClusterMixin,
+    TransformerMixin,
+    _fit_context,
+)
+from sklearn.utils.validation import check_is_fitted, validate_data
+
+from bblean_amd._merges import MergeCriterion
+from bblean_amd.bitbirch import BitBirch as _BitBirch
+from bblean_amd.fingerprints import pack_fingerprints, unpack_fingerprints
+from bblean_amd.similarity import jt_assign_packed, jt_dist_matrix_packed
+
+__all__ = ["BitBirch", "UnpackedBitBirch"]
+
+
+def _is_dev(x: object) -> bool:
+    return hasattr(x, "data_ptr") and getattr(x, "is_cuda", False)
+
+
+class BitBirch(
+    ClassNamePrefixFeaturesOutMixin,
+    ClusterMixin,
+    TransformerMixin,
+    BaseEstimator,
+    _BitBirch,
+):
+    r"""BitBIRCH clustering as a scikit-learn estimator.
+
+    Inputs are *packed* fingerprints by default; `UnpackedBitBirch` always takes unpacked ones.
+    See `bblean_amd.bitbirch.BitBirch` for the algorithm's parameters."""
+
+    _parameter_constraints: dict[str, list[tp.Any]] = {}
+
+    def __init__(
+        self,
+        *,
+        threshold: float = 0.65,
+        branching_factor: int = 50,
+        merge_criterion: str | MergeCriterion | None = None,
+        tolerance: float | None = None,
+        compute_labels: bool = True,
+    ):
+        super().__init__(
+            threshold=threshold,
+            branching_factor=branching_factor,
+            merge_criterion=merge_criterion,
+            tolerance=tolerance,
+        )
+        self.compute_labels = compute_labels
+
+    @_fit_context(prefer_skip_nested_validation=True)
+    def fit(  # type: ignore[override]
+        self, X, y=None, input_is_packed: bool = True, n_features: int | None = None
+    ) -> "BitBirch":
+        _BitBirch.fit(self, X, input_is_packed=input_is_packed, n_features=n_features)
+        order = self._leaf_order(True)  # largest cluster first, stable: get_centroids(sort=True)
+        packed = self._leaves()["cents"][order]
+        self.subcluster_centers_ = unpack_fingerprints(packed, self._n_features)
+        self.subcluster_labels_ = np.arange(1, len(packed) + 1)
+        self._n_features_out = len(packed)
+        # the operand of predict / transform: packed, and in HBM when the engine keeps its tree there
+        gather = getattr(self._engine, "gather_centroids", None)
+        self._packed_centers = gather(order, device_out=True) if gather is not None else np.ascontiguousarray(packed)
+        if self.compute_labels:
+            self.labels_ = self.get_assignments()
+        return self
+
+    @_fit_context(prefer_skip_nested_validation=True)
+    def partial_fit(  # type: ignore[no-untyped-def]
+        self, X=None, y=None, input_is_packed: bool = True, n_features: int | None = None
+    ) -> "BitBirch":
+        if X is None:
+            raise ValueError()
+        self.fit(X, input_is_packed=input_is_packed, n_features=n_features)
+        if self.compute_labels:
+            self.labels_ = self.get_assignments()
+        return self
+
+    # Overloaded since self.labels_ may not be set
+    def fit_predict(  # type: ignore[override]
+        self, X, y=None, input_is_packed: bool = True, n_features: int | None = None
+    ) -> NDArray[np.integer]:
+        self.fit(X, input_is_packed=input_is_packed, n_features=n_features)
+        if not self.compute_labels:
+            self.labels_ = self.get_assignments()
+        return self.labels_
+
+    def _packed_queries(self, X, input_is_packed: bool, n_features: int | None):  # type: ignore[no-untyped-def]
+        r"""Packed uint8 rows of the width the centroids have.  A device tensor is used in place (validate_data would
+        copy it to the host), so it is checked by hand; host input goes through validate_data as in the reference."""
+        nbytes = int(self._packed_centers.shape[1])
+        if _is_dev(X):
+            if not input_is_packed:
+                raise ValueError("device-resident input must be packed uint8")
+            if X.dim() != 2 or str(X.dtype) != "torch.uint8":
+                raise ValueError("device-resident input must be a 2-dimensional torch.uint8 tensor of packed rows")
+            if X.stride(1) != 1:
+                X = X.contiguous()
+        else:
+            X = validate_data(self, X, accept_sparse="csr", reset=False)
+            if hasattr(X, "toarray"):
+                X = X.toarray()
+            X = X.astype(np.uint8, copy=False)
+            if not input_is_packed:
+                X = pack_fingerprints(X)
+            elif n_features is not None and X.shape[1] * 8 != n_features:
+                X = pack_fingerprints(unpack_fingerprints(X, n_features))
+        if int(X.shape[1]) != nbytes:
+            raise ValueError(f"X has {int(X.shape[1])} packed bytes per row, the fitted centroids have {nbytes}")
+        return X
+
+    def predict(  # type: ignore[no-untyped-def]
+        self, X, input_is_packed: bool = True, n_features: int | None = None
+    ):
+        """Label (1..K) of the closest subcluster centroid of every row; a device tensor gives a device tensor."""
+        check_is_fitted(self)
+        dev = _is_dev(X)
+        idx = jt_assign_packed(self._packed_queries(X, input_is_packed, n_features), self._packed_centers)
+        if dev:
+            return idx.long() + 1
+        if _is_dev(idx):
+            idx = idx.cpu().numpy()
+        return self.subcluster_labels_[idx]
+
+    def transform(  # type: ignore[no-untyped-def]
+        self, X, input_is_packed: bool = True, n_features: int | None = None
+    ):
+        """Jaccard distance of every row to every subcluster centroid, float64 (n, K)."""
+        check_is_fitted(self)
+        return jt_dist_matrix_packed(self._packed_queries(X, input_is_packed, n_features), self._packed_centers)
+
+    def __sklearn_tags__(self):  # type: ignore[no-untyped-def]
+        tags = super().__sklearn_tags__()
+        tags.input_tags.sparse = True
+        return tags
+
+
+class UnpackedBitBirch(BitBirch):
+    r"""The same estimator; inputs are *unpacked* fingerprints always."""
+
+    def fit(  # type: ignore[no-untyped-def, override]
+        self, X, y=None, input_is_packed: bool = False, n_features: int | None = None
+    ):
+        return super().fit(X, y, input_is_packed=input_is_packed, n_features=n_features)
+
+    def partial_fit(  # type: ignore[no-untyped-def]
+        self, X, y=None, input_is_packed: bool = False, n_features: int | None = None
+    ):
+        return super().partial_fit(X, y, input_is_packed=input_is_packed, n_features=n_features)
+
+    def fit_predict(  # type: ignore[no-untyped-def, override]
+        self, X, y=None, input_is_packed: bool = False, n_features: int | None = None
+    ):
+        return super().fit_predict(X, y, input_is_packed=input_is_packed, n_features=n_features)
+
+    def predict(  # type: ignore[no-untyped-def]
+        self, X, input_is_packed: bool = False, n_features: int | None = None
+    ):
+        return super().predict(X, input_is_packed=input_is_packed, n_features=n_features)
+
+    def transform(  # type: ignore[no-untyped-def]
+        self, X, input_is_packed: bool = False, n_features: int | None = None
+    ):
+        return super().transform(X, input_is_packed=input_is_packed, n_features=n_features)

@@ -86,6 +86,25 @@ int bbh_jt_best_match(const uint8_t* queries, int64_t nq, const uint8_t* cents, 
                       int64_t nbytes, int32_t* out_idx, uint32_t* out_inter,
                       uint32_t* out_union, double* out_sims, void* stream);
 
+/* sklearn.BitBirch.predict's inner step (bblean/sklearn.py:123-137 = pairwise_distances_argmin, metric
+ * "jaccard"): out_idx[q] = FIRST index of the minimum of (u - i) / u over the nc centroid rows, distance 0
+ * where u == 0 (i = popcount of the AND, u = |q| + |c| - i).  An empty union therefore beats every other pair,
+ * which is where this differs from bbh_jt_best_match.  1 <= nc < 2^31; query rows q_stride bytes apart.
+ * out_inter / out_union: optional, the winning pair's exact counts (true union, 0 allowed).
+ * BBHIP_ASSIGN=bcnt|mfma forces the AND + popcount or the int8 matrix-core kernel (the latter: nbytes == 256,
+ * 16-byte aligned rows); unset = chosen by shape.  The result does not depend on the kernel. */
+int bbh_jt_assign(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* cents, int64_t nc,
+                  int64_t nbytes, int32_t* out_idx, uint32_t* out_inter, uint32_t* out_union, void* stream);
+
+/* sklearn.BitBirch.transform (sklearn.py:139-153 = pairwise_distances, metric "jaccard"): nq x nc float64,
+ * out[q * nc + m] = (u - i) / u as ONE division of the exact integers (not 1 - i / u), 0.0 where u == 0. */
+int bbh_jt_dist_matrix(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* cents, int64_t nc,
+                       int64_t nbytes, double* out, void* stream);
+
+/* Test hook: one v_mfma_i32_16x16x64_i8 with the operand lane maps bb_assign.hip documents.
+ * a: 16 x 64 int8, b: 64 x 16 int8, d: 16 x 16 int32 = a @ b, all row-major, host or device. */
+int bbh_mfma_i8_probe(const int8_t* a, const int8_t* b, int32_t* d, void* stream);
+
 /* unpack_fingerprints (similarity.cpp:145-214): packed n x nbytes -> n x n_features
  * uint8 of 0/1.  n_features must be a multiple of 8 (same restriction, :163-165). */
 int bbh_unpack(const uint8_t* packed, int64_t n, int64_t nbytes, int64_t n_features,
