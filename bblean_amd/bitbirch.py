@@ -17,6 +17,7 @@ file only keeps what the reference keeps on the host *around* that loop:
 """
 from __future__ import annotations
 
+import itertools
 import random
 import typing as tp
 import warnings
@@ -641,11 +642,42 @@ class BitBirch:
             for p, m in zip(order, lists)
         ]
 
-    # medoids: analysis helpers on the host (reference bitbirch.py:909-967)
+    # medoids (reference bitbirch.py:909-967): packed rows take ONE segmented call over all clusters
     def get_medoids_mol_ids(self, fps, sort=True, pack=True, global_clusters=False, input_is_packed=True, n_features=None):  # type: ignore[no-untyped-def]
-        from bblean_amd.similarity import jt_isim_medoid
+        from bblean_amd.similarity import _is_dev, _seg_fits, jt_compl_isim_segments, jt_isim_medoid
 
         members = self.get_cluster_mol_ids(sort=sort, global_clusters=global_clusters)
+        on_device = _is_dev(fps) and fps.dim() == 2 and str(fps.dtype) == "torch.uint8"
+        on_host = isinstance(fps, np.ndarray) and fps.ndim == 2 and fps.dtype == np.uint8
+        if input_is_packed and (on_device or on_host) and len(members):
+            nb = int(fps.shape[1])
+            nf = nb * 8 if n_features is None else int(n_features)
+            sizes = np.fromiter(map(len, members), dtype=np.int64, count=len(members))
+            if 0 < nf <= nb * 8 and nf % 8 == 0 and _seg_fits(nf, int(sizes.max())):
+                offsets = np.zeros(len(members) + 1, dtype=np.int64)
+                np.cumsum(sizes, out=offsets[1:])
+                if global_clusters:
+                    flat = np.fromiter(itertools.chain.from_iterable(members), dtype=np.int64, count=int(offsets[-1]))
+                else:  # the member lists are slices of the leaf table: gather them as arrays
+                    lv = self._leaves()
+                    beg = lv["beg"][self._leaf_order(sort)]
+                    flat = lv["members"][np.repeat(beg - offsets[:-1], sizes) + np.arange(int(offsets[-1]), dtype=np.int64)]
+                    flat = np.ascontiguousarray(flat, dtype=np.int64)
+                if on_device:
+                    import torch
+
+                    flat_t = torch.from_numpy(flat).to(fps.device)
+                    pos = jt_compl_isim_segments(fps, offsets, flat_t, nf, return_compl=False)[0]
+                    medoids = fps[flat_t[torch.from_numpy(offsets[:-1]).to(fps.device) + pos]][:, : nf // 8]
+                    if not pack:
+                        shifts = torch.arange(7, -1, -1, device=fps.device, dtype=torch.uint8)
+                        medoids = ((medoids.unsqueeze(-1) >> shifts) & 1).reshape(medoids.shape[0], nf)
+                    return {"medoids": medoids.contiguous(), "mol_ids": members}
+                pos = jt_compl_isim_segments(fps, offsets, flat, nf, return_compl=False)[0]
+                medoids = fps[flat[offsets[:-1] + pos]][:, : nf // 8]
+                if not pack:
+                    medoids = unpack_fingerprints(medoids, nf)
+                return {"medoids": medoids, "mol_ids": members}
         if input_is_packed:
             fps = unpack_fingerprints(fps, n_features)
         medoids = np.zeros((len(members), fps.shape[1]), dtype=np.uint8)

@@ -65,6 +65,16 @@ class _Clustering:
             return [_sim.centroid(c, input_is_packed=self.given_packed, n_features=self.n_features, pack=True)
                     for c in self.given]
         if spec == "medoid":
+            rows = self.given
+            if (self.given_packed and rows and all(isinstance(c, np.ndarray) and c.ndim == 2 and c.dtype == np.uint8
+                                                    and len(c) and c.shape[1] == rows[0].shape[1] for c in rows)):
+                nb = rows[0].shape[1]
+                nf = nb * 8 if self.n_features is None else int(self.n_features)
+                if 0 < nf <= nb * 8 and nf % 8 == 0 and _sim._seg_fits(nf, max(self.sizes)):
+                    # one segmented call over the concatenated clusters instead of a call per row
+                    offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
+                    pos = _sim.jt_compl_isim_segments(np.concatenate(rows), offsets, n_features=nf, return_compl=False)[0]
+                    return [c[int(i)][: nf // 8] for c, i in zip(rows, pos)]
             return [_sim.jt_isim_medoid(c, input_is_packed=self.given_packed, n_features=self.n_features, pack=True)[1]
                     for c in self.given]
         raise ValueError(f"Unknown arg {spec} use 'medoids|centroids'")

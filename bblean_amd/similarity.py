@@ -42,6 +42,7 @@ __all__ = [
     "jt_best_match_packed",
     "jt_assign_packed",
     "jt_dist_matrix_packed",
+    "jt_compl_isim_segments",
 ]
 
 
@@ -463,8 +464,128 @@ def jt_most_dissimilar_packed(
 
 
 # ---------------------------------------------------- analysis-side composites ----
+def _seg_fits(n_features: int, largest: int) -> bool:
+    r"""The exact uint64 moments of a set of `largest` rows fit (bbhip.h, bbh_compl_isim_segments)."""
+    return largest < 2**31 and n_features * largest * largest < 2**63
+
+
+def _seg_host_index(a: object, what: str) -> NDArray[np.int64]:
+    arr = np.asarray(a)
+    if arr.ndim != 1 or arr.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be a 1-dimensional integer array")
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
+def jt_compl_isim_segments(fps, offsets, members=None, n_features=None, return_compl=True):  # type: ignore[no-untyped-def]
+    r"""Complementary iSIM (`jt_compl_isim`) and medoid position (`jt_isim_medoid`) of ``k`` independent sets of packed
+    rows in one call.  Set ``g`` is ``fps[offsets[g]:offsets[g + 1]]``, or ``fps[members[offsets[g]:offsets[g + 1]]]``
+    when ``members`` is given.  Returns ``(positions, compl)``: int64 ``[k]``, the position INSIDE each set of the first
+    minimum of its values (0 for sets of 1 or 2 rows), and float64 ``[offsets[-1]]`` in set order (NaN for sets of 1 or 2
+    rows), or ``None`` with ``return_compl=False``.  Bit for bit the reference's values (_py_similarity.py:65-117).
+
+    NumPy in -> NumPy out; device tensors in -> device tensors out, on the current stream.  Host rows beyond a slab
+    (`BBHIP_SLAB_KB`) go through in slabs of whole sets, gathered on the host with one `take` per slab."""
+    dev = _is_dev(fps)
+    if dev:
+        if fps.dim() != 2 or str(fps.dtype) != "torch.uint8" or fps.stride(1) != 1:
+            raise ValueError("fps must be a 2-dimensional uint8 array of packed rows")
+        rows, n_rows, nb, stride = fps, int(fps.shape[0]), int(fps.shape[1]), int(fps.stride(0))
+    else:
+        rows = np.asarray(fps)
+        if rows.ndim != 2 or rows.dtype != np.uint8:
+            raise ValueError("fps must be a 2-dimensional uint8 array of packed rows")
+        if rows.shape[0] and (rows.strides[1] != 1 or rows.strides[0] < rows.shape[1]):
+            rows = np.ascontiguousarray(rows)
+        n_rows, nb = rows.shape
+        stride = int(rows.strides[0]) if n_rows else nb
+    nf = nb * 8 if n_features is None else int(n_features)
+    if nf <= 0 or nf % 8 != 0 or nf > nb * 8:
+        raise ValueError("Only n_features divisible by 8 (and within the packed width) is supported")
+    off_dev = _is_dev(offsets)
+    mem_dev = _is_dev(members)
+    if off_dev:
+        if offsets.dim() != 1 or str(offsets.dtype) != "torch.int64" or not offsets.is_contiguous():
+            raise ValueError("offsets must be a contiguous 1-dimensional int64 tensor")
+        off = offsets
+        k = int(off.shape[0]) - 1
+    else:
+        off = _seg_host_index(offsets, "offsets")
+        k = len(off) - 1
+    if k < 1:
+        raise ValueError("offsets must name at least one set")
+    if mem_dev:
+        if members.dim() != 1 or str(members.dtype) != "torch.int64" or not members.is_contiguous():
+            raise ValueError("members must be a contiguous 1-dimensional int64 tensor")
+        mem = members
+        n_mem = int(mem.shape[0])
+    elif members is not None:
+        mem = _seg_host_index(members, "members")
+        n_mem = len(mem)
+        if n_mem and (int(mem.min()) < 0 or int(mem.max()) >= n_rows):
+            raise ValueError("members must be row numbers of fps")
+    else:
+        mem, n_mem = None, n_rows
+    if not off_dev:
+        if off[0] != 0:
+            raise ValueError("offsets must start at 0")
+        sizes = np.diff(off)
+        if (sizes < 0).any():
+            raise ValueError("offsets must not decrease")
+        if (sizes == 0).any():
+            raise ValueError("Size of fingerprints set must be > 0")
+        if int(off[-1]) > n_mem:
+            raise ValueError("offsets name more rows than there are")
+        if not _seg_fits(nf, int(sizes.max())):
+            raise ValueError("a set is too large for exact 64-bit moments: n_features * m * m must stay below 2**63")
+    lib = _lib.load()
+    if dev or off_dev or mem_dev:
+        import torch
+
+        if not dev:
+            raise ValueError("offsets / members on the device need fps on the device")
+        d = rows.device
+        total = int(off[-1].item()) if off_dev else int(off[-1])
+        if total < 0 or total > n_mem:
+            raise ValueError("offsets name more rows than there are")
+        med_t = torch.empty(k, dtype=torch.int64, device=d)
+        compl_t = torch.empty(total, dtype=torch.float64, device=d) if return_compl else None
+        st = torch.cuda.current_stream(d).cuda_stream
+        _lib.check(lib.bbh_compl_isim_segments(_lib.ptr(rows), n_rows, nb, stride, _lib.ptr(mem), _lib.ptr(off), k, nf,
+                                               _lib.ptr(compl_t), _lib.ptr(med_t), st))
+        return med_t, compl_t
+    total = int(off[-1])
+    med = np.empty(k, dtype=np.int64)
+    compl = np.empty(total, dtype=np.float64) if return_compl else None
+    slab = _slab_rows(nb)
+    if total <= slab and (mem is None or n_rows <= slab):
+        part = rows if mem is not None else rows[:total]
+        _lib.check(lib.bbh_compl_isim_segments(part.ctypes.data, len(part), nb, stride, _lib.ptr(mem), off.ctypes.data, k, nf,
+                                               _lib.ptr(compl), med.ctypes.data, None))
+        return med, compl
+    g0 = 0
+    while g0 < k:  # slabs of whole sets; a set larger than a slab is a slab of its own
+        g1 = int(np.searchsorted(off, off[g0] + slab, side="right")) - 1
+        g1 = min(k, max(g1, g0 + 1))
+        lo, hi = int(off[g0]), int(off[g1])
+        part = np.ascontiguousarray(rows[lo:hi]) if mem is None else rows.take(mem[lo:hi], axis=0)
+        sub = np.ascontiguousarray(off[g0:g1 + 1] - lo)
+        _lib.check(lib.bbh_compl_isim_segments(part.ctypes.data, hi - lo, nb, nb, None, sub.ctypes.data, g1 - g0, nf,
+                                               compl[lo:hi].ctypes.data if compl is not None else None,
+                                               med[g0:g1].ctypes.data, None))
+        g0 = g1
+    return med, compl
+
+
+def _is_packed_u8(fps: object) -> bool:
+    return isinstance(fps, np.ndarray) and fps.dtype == np.uint8 and fps.ndim == 2
+
+
 def jt_compl_isim(fps: NDArray[np.uint8], input_is_packed: bool = True, n_features: int | None = None) -> NDArray[np.float64]:
-    r"""Complementary iSIM of every row (_py_similarity.py:65-83)."""
+    r"""Complementary iSIM of every row (_py_similarity.py:65-83).  Packed uint8 rows: one segmented call."""
+    if input_is_packed and _is_packed_u8(fps):
+        nf = fps.shape[1] * 8 if n_features is None else int(n_features)
+        if len(fps) >= 3 and nf > 0 and nf % 8 == 0 and nf <= fps.shape[1] * 8 and _seg_fits(nf, len(fps)):
+            return jt_compl_isim_segments(fps, np.array([0, len(fps)], dtype=np.int64), n_features=nf)[1]
     if input_is_packed:
         fps = unpack_fingerprints(fps, n_features)
     n_objects = len(fps) - 1
@@ -479,6 +600,13 @@ def jt_isim_medoid(fps: NDArray[np.uint8], input_is_packed: bool = True, n_featu
     r"""(_py_similarity.py:91-117)"""
     if not fps.size:
         raise ValueError("Size of fingerprints set must be > 0")
+    if input_is_packed and _is_packed_u8(fps):
+        nf = fps.shape[1] * 8 if n_features is None else int(n_features)
+        if len(fps) >= 3 and nf > 0 and nf % 8 == 0 and nf <= fps.shape[1] * 8 and _seg_fits(nf, len(fps)):
+            idx = int(jt_compl_isim_segments(fps, np.array([0, len(fps)], dtype=np.int64), n_features=nf,
+                                             return_compl=False)[0][0])
+            m = unpack_fingerprints(fps[idx], n_features)  # only the winning row
+            return (idx, pack_fingerprints(m)) if pack else (idx, m)
     if input_is_packed:
         fps = unpack_fingerprints(fps, n_features)
     idx = 0 if len(fps) < 3 else int(np.argmin(jt_compl_isim(fps, input_is_packed=False)))

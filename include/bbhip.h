@@ -137,6 +137,19 @@ int bbh_isim_from_sum(const void* linear_sum, int32_t ls_width, int64_t n_featur
 int bbh_isim_rows(const uint8_t* arr, int64_t n, int64_t n_cols, int packed,
                   int64_t n_features, double* out, int* warn, void* stream);
 
+/* jt_compl_isim / jt_isim_medoid (_py_similarity.py:65-117) for k independent sets of packed rows in one call.
+ * Set g is rows[offsets[g] .. offsets[g+1]) when members == NULL, else rows[members[i]] for i in that range
+ * (offsets: k + 1 non-decreasing int64, offsets[0] == 0; members: offsets[k] int64 in [0, n_rows)).
+ * out_compl: optional, offsets[k] float64 in set order; out_medoid: optional, k int64 = position INSIDE the set of
+ * the FIRST minimum of its complementary iSIMs.  Sets of 1 or 2 rows: NaN / position 0; an empty set is
+ * BBH_ERR_INVALID, and so are an entry of members that is not a row and a set with n_features * m * m >= 2^63
+ * (the exact uint64 moments would not fit).  n_features % 8 == 0, n_features <= nbytes * 8.  All pointers host or
+ * device.  Recorded by bbh_profile_* as "compl_isim_seg/small" (sets a single wave takes) and
+ * "compl_isim_seg/large", "compl_isim_seg" is their sum; units = rows. */
+int bbh_compl_isim_segments(const uint8_t* rows, int64_t n_rows, int64_t nbytes, int64_t row_stride,
+                            const int64_t* members, const int64_t* offsets, int64_t k, int64_t n_features,
+                            double* out_compl, int64_t* out_medoid, void* stream);
+
 /* The pair loop of metrics.jt_isim_dunn (bblean/metrics.py:186-199) in one call: min over all pairs i < j of
  * 1 - jt_isim_from_sum(sums[i] + sums[j], sizes[i] + sizes[j]); 1.0 when there are fewer than two clusters.
  * sums: k x n_features uint64 column sums (host or device), sizes: k uint64; out: host double. */
