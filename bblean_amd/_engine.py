@@ -9,6 +9,8 @@ does that - `HipEngine` is the only engine the package constructs.
 from __future__ import annotations
 
 import ctypes as C
+import os
+import typing as tp
 
 import numpy as np
 from numpy.typing import NDArray
@@ -408,6 +410,55 @@ class HipEngine:
     def compact(self, seal: bool = True) -> None:
         r"""Compact the node pools now (tests; the engine does it on its own when large pools have to grow)."""
         _lib.check(self._lib.bbh_tree_compact(self._h, 1 if seal else 0))
+
+    # -- persistence (include/bbhip.h "Tree images") -----------------------------------------
+    @staticmethod
+    def image_min_stage(n_features: int) -> int:
+        r"""Smallest `stage_bytes` `save_image` / `load_image` accept for trees of `n_features` (one group of the image)."""
+        return 64 * (4 * (((int(n_features) // 8) + 15) // 16 * 16) + 176)
+
+    def save_image(self, fileobj: tp.Any, stage_bytes: int = 0) -> int:
+        r"""Write the tree's image at `fileobj`'s position (a binary file object with a descriptor); the library writes
+        straight to the descriptor.  `stage_bytes`: HBM and pinned host memory the call may hold (0: 64 MiB).  Returns the
+        image's bytes; the tree is left exactly as it was."""
+        fileobj.flush()
+        fd = fileobj.fileno()
+        os.lseek(fd, fileobj.tell(), os.SEEK_SET)
+        written = C.c_uint64(0)
+        _lib.check(self._lib.bbh_tree_save_fd(self._h, fd, int(stage_bytes), C.byref(written)))
+        fileobj.seek(os.lseek(fd, 0, os.SEEK_CUR))
+        return int(written.value)
+
+    @classmethod
+    def load_image(cls, fileobj: tp.Any, device: int = 0, stage_bytes: int = 0) -> "HipEngine":
+        r"""A new engine from the image at `fileobj`'s position (checked as `check_image` checks it before the device
+        sees it); the position is left behind the image."""
+        lib = _lib.load()
+        fd = fileobj.fileno()
+        os.lseek(fd, fileobj.tell(), os.SEEK_SET)
+        pos = fileobj.tell()
+        handle = C.c_void_p()
+        _lib.check(lib.bbh_tree_load_fd(C.byref(handle), fd, int(device), int(stage_bytes)))
+        n_features = int(np.frombuffer(os.pread(fd, 4, pos + 28), dtype="<i4")[0])  # (the checked header: int32 at byte 28)
+        fileobj.seek(os.lseek(fd, 0, os.SEEK_CUR))
+        self = cls.__new__(cls)
+        self._lib = lib
+        self.device = int(device)
+        self._h = handle
+        self.n_features = n_features
+        self.nbytes = (self.n_features + 7) // 8
+        return self
+
+    @staticmethod
+    def check_image(fileobj: tp.Any) -> int:
+        r"""Validate the image at `fileobj`'s position on the host (no device needed): RuntimeError with the library's
+        message if anything is wrong, else the image's bytes.  The position does not move."""
+        lib = _lib.load()
+        fd = fileobj.fileno()
+        os.lseek(fd, fileobj.tell(), os.SEEK_SET)
+        n = C.c_uint64(0)
+        _lib.check(lib.bbh_tree_image_check_fd(fd, C.byref(n)))
+        return int(n.value)
 
     def close(self) -> None:
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -70,6 +70,9 @@ _PROTOTYPES = {
     "bbh_tree_sys_counts": (_int, [_vp, _vp]),
     "bbh_tree_memory": (_int, [_vp, _vp]),
     "bbh_tree_compact": (_int, [_vp, _i32]),
+    "bbh_tree_save_fd": (_int, [_vp, _int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "bbh_tree_load_fd": (_int, [C.POINTER(_vp), _int, _i32, C.c_uint64]),
+    "bbh_tree_image_check_fd": (_int, [_int, C.POINTER(C.c_uint64)]),
     "bbh_profile_enable": (_int, [_int]),
     "bbh_profile_reset": (_int, []),
     "bbh_profile_get": (_int, [C.c_char_p, C.POINTER(_i64), C.POINTER(_f64)]),

@@ -17,8 +17,14 @@ file only keeps what the reference keeps on the host *around* that loop:
 """
 from __future__ import annotations
 
+import io
 import itertools
+import json
+import os
+import pickle
 import random
+import struct
+import tempfile
 import typing as tp
 import warnings
 from pathlib import Path
@@ -36,6 +42,16 @@ __all__ = ["BitBirch", "set_merge", "fit_concurrently"]
 _Input = tp.Union[NDArray[np.integer], list]
 
 _BITBIRCH_INSTANCES: "WeakSet[BitBirch]" = WeakSet()
+
+# tree files (BitBirch.save / load, INTEGRATION.md "Tree files")
+_TREE_FILE_MAGIC = b"BBAMDTREE\x00"
+_TREE_FILE_FORMAT = "bblean_amd.tree"
+_TREE_FILE_VERSION = 1
+
+
+class _BadTreeFile(Exception):
+    r"""What `BitBirch.load` turns into a ValueError that names the path."""
+
 _global_merge_accept: MergeCriterion | None = None
 
 
@@ -944,11 +960,243 @@ class BitBirch:
         self._n_global_clusters = n_clusters if num > n_clusters else num
         return self
 
-    def save(self, path: Path | str) -> None:
-        raise NotImplementedError(
-            "whole-tree pickling (reference bitbirch.py:1321-1353) is not provided; "
-            "checkpoint with _bf_to_np() tables instead"
-        )
+    # ------------------------------------------------------------- persistence ----
+    def save(self, path: Path | str, *, stage_bytes: int = 0) -> None:
+        r"""Write the fitted tree to ONE file (INTEGRATION.md "Tree files"): a JSON header with the configuration, the
+        host bookkeeping as ``.npy`` arrays and the engine's tree image, which the library writes straight to the file.
+        The reference pickles the whole object (bitbirch.py:1321-1339); this file is no pickle and `load` unpickles nothing.
+        A custom `MergeCriterion` object cannot be stored: only the built-in criteria, by name."""
+        path = Path(path)
+        self._check_storable()  # (before the target is touched: a refused save leaves an existing file as it was)
+        tmp = path.with_name(f"{path.name}.{os.getpid()}.part")
+        try:
+            with open(tmp, "wb") as f:
+                self._write_container(f, stage_bytes)
+            os.replace(tmp, path)  # a save that fails half-way leaves nothing under the final name
+        except BaseException:
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+            raise
+
+    @classmethod
+    def load(
+        cls,
+        path: Path | str,
+        device: int = 0,
+        *,
+        stage_bytes: int = 0,
+        _engine_factory: tp.Callable[..., tp.Any] | None = None,
+        _engine_loader: tp.Callable[..., tp.Any] | None = None,
+    ) -> "BitBirch":
+        r"""The tree `save` wrote, on `device` (reference bitbirch.py:1341-1353).  The saved merge criterion and tolerance
+        are restored whether or not the module-level `set_merge` is in force.  `_engine_factory` / `_engine_loader` are
+        test hooks like the constructor's: the loader - by default the factory's `load_image`, if it has one - is called
+        with (file object, device) where the image starts.
+        Anything wrong with the file - not a tree file, another version, truncated, an image that fails the library's
+        check - is a ValueError that names the path."""
+        path = Path(path)
+        self = cls.__new__(cls)
+        try:
+            with open(path, "rb") as f:
+                self._read_container(f, device, stage_bytes, _engine_factory, _engine_loader)
+        except _BadTreeFile as exc:
+            raise ValueError(f"{path}: {exc}") from None
+        return self
+
+    def _check_storable(self) -> None:
+        fn = self._merge_accept_fn
+        if fn.name not in BUILTIN_MERGES or type(fn) is not MergeCriterion or (fn.n_max, fn.decay) != (1000, 1e-3):
+            raise ValueError(
+                f"a custom MergeCriterion ({fn!r}) cannot be stored in a tree file: only the built-in criteria, by name"
+            )
+        if self._engine is not None and not hasattr(self._engine, "save_image"):
+            raise ValueError(f"the engine {type(self._engine).__name__} cannot write a tree image")
+
+    def _write_container(self, f: tp.BinaryIO, stage_bytes: int = 0) -> None:
+        self._check_storable()  # (`save` has asked already, before it touched the target; __getstate__ comes here directly)
+        fn = self._merge_accept_fn
+        has_image = self._engine is not None
+        arrays: dict[str, NDArray] = {}
+        if self._log_leaf:
+            arrays["log_leaf"] = np.concatenate(self._log_leaf).astype(np.uint32, copy=False)
+            arrays["log_ids"] = np.concatenate(self._log_ids).astype(np.int64, copy=False)
+            counts = [c for c in self._log_counts if c is not None]
+            arrays["log_counts"] = np.concatenate(counts).astype(np.int64, copy=False) if counts else np.zeros(0, dtype=np.int64)
+        if self._global_clustering_centroid_labels is not None:
+            arrays["global_labels"] = np.asarray(self._global_clustering_centroid_labels, dtype=np.int64)
+        header = {
+            "format": _TREE_FILE_FORMAT,
+            "version": _TREE_FILE_VERSION,
+            "threshold": float(self.threshold),
+            "branching_factor": int(self.branching_factor),
+            "merge_criterion": fn.name,
+            "tolerance": None if fn.tolerance is None else float(fn.tolerance),
+            "n_features": int(self._n_features),
+            "num_fitted_fps": int(self._num_fitted_fps),
+            "is_init": bool(self._is_init),
+            "internal_released": bool(self._internal_released),
+            "n_global_clusters": int(self._n_global_clusters),
+            # per fit call: [leaf ids, member ids, counts or -1 (a `fit` call: one id per element)]
+            "log_calls": [[int(l.size), int(i.size), -1 if c is None else int(c.size)]
+                          for l, i, c in zip(self._log_leaf, self._log_ids, self._log_counts)],
+            "arrays": list(arrays),
+            "has_image": has_image,
+        }
+        blob = json.dumps(header).encode("utf-8")
+        f.write(_TREE_FILE_MAGIC + struct.pack("<II", _TREE_FILE_VERSION, len(blob)) + blob)
+        for arr in arrays.values():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arr), allow_pickle=False)
+            f.write(struct.pack("<Q", buf.getbuffer().nbytes))
+            f.write(buf.getbuffer())
+        if has_image:
+            at = f.tell()
+            f.write(struct.pack("<Q", 0))
+            n = int(self._engine.save_image(f, stage_bytes) if stage_bytes else self._engine.save_image(f))
+            end = f.tell()
+            f.seek(at)
+            f.write(struct.pack("<Q", n))
+            f.seek(end)
+        f.flush()
+
+    def _read_container(self, f, device, stage_bytes, engine_factory, engine_loader):  # type: ignore[no-untyped-def]
+        def take(n: int, what: str) -> bytes:
+            b = f.read(n)
+            if len(b) != n:
+                raise _BadTreeFile(f"the file is truncated ({what})")
+            return b
+
+        head = take(len(_TREE_FILE_MAGIC) + 8, "header")
+        if head[: len(_TREE_FILE_MAGIC)] != _TREE_FILE_MAGIC:
+            raise _BadTreeFile("not a BitBirch tree file (wrong magic)")
+        version, n_json = struct.unpack("<II", head[len(_TREE_FILE_MAGIC):])
+        if version != _TREE_FILE_VERSION:
+            raise _BadTreeFile(f"tree file version {version} is not supported (this package reads version {_TREE_FILE_VERSION})")
+        try:
+            header = json.loads(take(n_json, "JSON header").decode("utf-8"))
+            if header["format"] != _TREE_FILE_FORMAT or header["version"] != version:
+                raise KeyError("format")
+            fn = get_merge_accept_fn(header["merge_criterion"], 0.05 if header["tolerance"] is None else float(header["tolerance"]))
+            names = [str(a) for a in header["arrays"]]
+            calls = [(int(a), int(b), int(c)) for a, b, c in header["log_calls"]]
+        except _BadTreeFile:
+            raise
+        except Exception as exc:
+            raise _BadTreeFile(f"the header is not that of a tree file ({type(exc).__name__}: {exc})") from None
+        arrays: dict[str, NDArray] = {}
+        for name in names:
+            (n,) = struct.unpack("<Q", take(8, f"array {name}"))
+            try:
+                arrays[name] = np.lib.format.read_array(io.BytesIO(take(n, f"array {name}")), allow_pickle=False)
+            except _BadTreeFile:
+                raise
+            except Exception as exc:
+                raise _BadTreeFile(f"array {name} cannot be read ({exc})") from None
+        leaf = arrays.get("log_leaf", np.zeros(0, dtype=np.uint32))
+        ids = arrays.get("log_ids", np.zeros(0, dtype=np.int64))
+        cnts = arrays.get("log_counts", np.zeros(0, dtype=np.int64))
+        if (sum(a for a, _, _ in calls), sum(b for _, b, _ in calls), sum(max(c, 0) for _, _, c in calls)) != (leaf.size, ids.size, cnts.size):
+            raise _BadTreeFile("the per-call lengths do not match the bookkeeping arrays")
+        engine = None
+        if header["has_image"]:
+            (n_image,) = struct.unpack("<Q", take(8, "image length"))
+            at = f.tell()
+            f.seek(0, 2)
+            if f.tell() - at < n_image:
+                raise _BadTreeFile("the file is truncated (tree image)")
+            f.seek(at)
+            loader = engine_loader if engine_loader is not None else getattr(engine_factory, "load_image", None)
+            if loader is None:
+                from bblean_amd._engine import HipEngine
+
+                try:  # (host code: a bad image is refused here, before a device is asked for)
+                    if HipEngine.check_image(f) != n_image:
+                        raise RuntimeError("the image's length differs from the recorded one")
+                except RuntimeError as exc:
+                    raise _BadTreeFile(str(exc)) from None
+                loader = HipEngine.load_image if not stage_bytes else (lambda fo, dev: HipEngine.load_image(fo, dev, stage_bytes))
+            engine = loader(f, device)
+            # The two halves must describe one tree.  Only the width is fixed for a tree's life: threshold, branching
+            # factor and criterion may be changed between fits and reach the engine with the next one
+            # (_push_merge_to_engine), so the header's values are the ones that hold.
+            width = getattr(engine, "n_features", None)
+            if width is not None and int(width) != int(header["n_features"]):
+                close = getattr(engine, "close", None)
+                if close is not None:
+                    close()
+                raise _BadTreeFile(f"the header records {header['n_features']} features and the tree image holds {width}")
+        # everything was read: only now does the object come into being
+        self.threshold = header["threshold"]
+        self.branching_factor = header["branching_factor"]
+        self._merge_accept_fn = fn
+        self._device = device
+        self._engine_factory = engine_factory
+        self._engine = engine
+        self._n_features = int(header["n_features"])
+        self._num_fitted_fps = int(header["num_fitted_fps"])
+        self._is_init = bool(header["is_init"])
+        self._internal_released = bool(header["internal_released"])
+        self._log_leaf, self._log_counts, self._log_ids = [], [], []
+        a0 = b0 = c0 = 0
+        for a, b, c in calls:
+            self._log_leaf.append(leaf[a0:a0 + a])
+            self._log_ids.append(ids[b0:b0 + b])
+            self._log_counts.append(None if c < 0 else cnts[c0:c0 + c])
+            a0, b0, c0 = a0 + a, b0 + b, c0 + max(c, 0)
+        self._cache = {}
+        self._global_clustering_centroid_labels = arrays.get("global_labels")
+        self._n_global_clusters = int(header["n_global_clusters"])
+        _BITBIRCH_INSTANCES.add(self)
+
+    # pickle (and copy.deepcopy): the state is the tree file as bytes plus whatever else a subclass keeps on the instance -
+    # the scikit-learn estimators' fitted attributes; BaseEstimator's own __getstate__ / __setstate__ call these through super()
+    _PICKLE_SKIP: tp.ClassVar[frozenset] = frozenset()
+    _OWN_ATTRS: tp.ClassVar[frozenset] = frozenset({
+        "threshold", "branching_factor", "_merge_accept_fn", "_device", "_engine", "_n_features", "_num_fitted_fps", "_is_init",
+        "_internal_released", "_log_leaf", "_log_counts", "_log_ids", "_cache", "_global_clustering_centroid_labels",
+        "_n_global_clusters"})
+
+    def __getstate__(self) -> dict[str, tp.Any]:
+        with tempfile.TemporaryFile() as f:  # (the same code path as `save`: the library writes to a descriptor)
+            self._write_container(f)
+            f.seek(0)
+            blob = f.read()
+        extra = {k: v for k, v in self.__dict__.items() if k not in self._OWN_ATTRS and k not in self._PICKLE_SKIP}
+        return {"_tree_file": blob, "_device": self._device, "_extra": extra}
+
+    def __reduce_ex__(self, protocol: int):  # type: ignore[no-untyped-def]
+        rv = super().__reduce_ex__(protocol)
+        if protocol >= 5 and isinstance(rv, tuple) and len(rv) >= 3 and isinstance(rv[2], dict) and "_tree_file" in rv[2]:
+            state = dict(rv[2])
+            state["_tree_file"] = pickle.PickleBuffer(state["_tree_file"])  # out-of-band when the pickler has a buffer_callback
+            rv = rv[:2] + (state,) + rv[3:]
+        return rv
+
+    def __setstate__(self, state: dict[str, tp.Any]) -> None:
+        # sklearn's BaseEstimator.__setstate__ reaches this through super() and takes an AttributeError to mean "no
+        # __setstate__ above me", then fills __dict__ with the raw state: one raised in here must not look like that
+        try:
+            self._set_state(state)
+        except AttributeError as exc:
+            raise RuntimeError(f"restoring a pickled {type(self).__name__} failed: {exc!r}") from exc
+
+    def _set_state(self, state: dict[str, tp.Any]) -> None:
+        extra = dict(state["_extra"])
+        with tempfile.TemporaryFile() as f:
+            f.write(memoryview(state["_tree_file"]))
+            f.flush()
+            f.seek(0)
+            try:
+                self._read_container(f, state["_device"], 0, extra.pop("_engine_factory", None), None)
+            except _BadTreeFile as exc:
+                raise ValueError(f"pickled tree: {exc}") from None
+        self.__dict__.update(extra)
+        self._after_load()
+
+    def _after_load(self) -> None:
+        r"""Hook for subclasses: rebuild what `_PICKLE_SKIP` left out."""
 
     def __repr__(self) -> str:
         fn = self._merge_accept_fn

@@ -4159,3 +4159,5 @@ extern "C" int bbh_tree_stats(bbh_tree* t, uint64_t* out8) {
     }
     return BBH_OK;
 }
+
+#include "bb_tree_image.inc"

@@ -302,7 +302,8 @@ def run_multiround_bitbirch(
     tree = _merge_one_tree_streaming(prev_pairs(round_idx), threshold=threshold + midsection_threshold_change,
                                      criterion=final_merge_criterion, **common)
     if save_tree:
-        raise NotImplementedError("whole-tree pickling is not provided (the reference's --save-tree is broken too)")
+        # (a tree file, not a pickle - INTEGRATION.md "Tree files"; the reference means to write bitbirch.pkl here)
+        tree.save(out_dir / "bitbirch.tree")
     _write_outputs(out_dir, tree, save_centroids)
     timer.end_timing(f"round-{round_idx}")
     if cleanup:

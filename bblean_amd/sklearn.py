@@ -50,6 +50,7 @@ class BitBirch(
     See `bblean_amd.bitbirch.BitBirch` for the algorithm's parameters."""
 
     _parameter_constraints: dict[str, list[tp.Any]] = {}
+    _PICKLE_SKIP = frozenset({"_packed_centers"})  # a device tensor: rebuilt from the loaded tree (_after_load)
 
     def __init__(
         self,
@@ -84,6 +85,15 @@ class BitBirch(
         if self.compute_labels:
             self.labels_ = self.get_assignments()
         return self
+
+    def _after_load(self) -> None:
+        if hasattr(self, "subcluster_centers_"):  # fitted: the operand of predict / transform, as `fit` builds it
+            order = self._leaf_order(True)
+            gather = getattr(self._engine, "gather_centroids", None)
+            if gather is not None:
+                self._packed_centers = gather(order, device_out=True)
+            else:
+                self._packed_centers = np.ascontiguousarray(self._leaves()["cents"][order])
 
     @_fit_context(prefer_skip_nested_validation=True)
     def partial_fit(  # type: ignore[no-untyped-def]

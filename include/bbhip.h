@@ -270,6 +270,38 @@ int bbh_tree_memory(bbh_tree* t, uint64_t* out8);
  * back to full capacity.  Results of later calls do not depend on when or whether this ran. */
 int bbh_tree_compact(bbh_tree* t, int32_t seal);
 
+/* Tree images: one fitted tree as a self-contained, relocatable byte stream (INTEGRATION.md "Tree files" has the layout;
+ * the reference pickles its Python node objects, bitbirch.py:1321-1353).  An image holds every live node at the capacity of
+ * a sealed node (the root at full capacity), the used prefixes of the cluster-feature pools, the counters, the statistics
+ * of bbh_tree_stats and the configuration (branching factor, n_features, threshold, criterion, tolerance and its table);
+ * it holds no pool capacity, no profile or kernel-choice state.
+ *
+ * bbh_tree_save_fd writes the image at fd's current offset and leaves the tree exactly as it was (no pool is reallocated,
+ * no node id changes).  Beyond two uint32 per used block of the node pools (and the scan's few KB) it holds `stage_bytes`
+ * of HBM and as much pinned host memory: the image is produced and written in ranges of that size.  stage_bytes == 0
+ * means 64 MiB; the smallest value accepted is BBH_TREE_IMAGE_MIN_STAGE(n_features), anything in between is rounded
+ * down to a multiple of it.  The bytes written do not depend on stage_bytes.  *written (optional) = bytes of the image.
+ *
+ * bbh_tree_load_fd reads an image from fd's current offset into a NEW tree on `device` (pools sized as a compaction sizes
+ * them: what is live and a quarter more) and leaves the offset behind the image.  The handle is accepted by every other
+ * entry point; its nodes are sealed, insertions thaw what they reach, and no result depends on that (bbh_tree_compact).
+ * The image is checked as bbh_tree_image_check_fd checks it BEFORE the device sees any of it.
+ *
+ * bbh_tree_image_check_fd is host code and needs no device: magic, version, byte order, section lengths against the
+ * header's counts, truncation; then the structure, from headers, links and row records alone (centroid bytes are never
+ * read): every child link and leaf-chain link names a block that starts a live node, lengths <= capacities <= bf + 1,
+ * every cluster-feature slot lies below its tier's count (both words of a leaf row that carry one: the row record's and
+ * the link word; rows of internal nodes must name the uint32 tier), the leaf chain visits every leaf once and ends,
+ * every internal node has a child, every node hangs off the root once and every leaf lies on the recorded depth.  It keeps 32 bytes of host memory per image block while it
+ * runs and leaves fd's offset where it was.  Anything wrong: BBH_ERR_INVALID and a message.
+ * check and load read with pread: fd must be a regular file.  Profile records: "tree_image/save", "tree_image/load"
+ * (the device part of a call; units = image bytes). */
+#define BBH_TREE_IMAGE_MIN_STAGE(n_features) \
+    ((uint64_t)64 * (4 * ((((uint64_t)(n_features) / 8) + 15) / 16 * 16) + 176))
+int bbh_tree_save_fd(bbh_tree* t, int fd, uint64_t stage_bytes, uint64_t* written);
+int bbh_tree_load_fd(bbh_tree** out, int fd, int32_t device, uint64_t stage_bytes);
+int bbh_tree_image_check_fd(int fd, uint64_t* image_bytes);
+
 /* Per-kernel timing with HIP events on the stream each kernel is launched on.
  * bbh_profile_enable(1) turns it on; bbh_profile_get returns launches and summed
  * milliseconds for the kernel called `name` ("jt_arr_vec", "tree_insert", ...; the tree kernels are recorded as
