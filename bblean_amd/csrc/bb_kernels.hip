@@ -317,6 +317,11 @@ __global__ __launch_bounds__(256) void k_arr_vec_generic(const uint8_t* __restri
     }
 }
 
+// bytes of n rows of nbytes each, row_stride apart: the last row ends after nbytes, not after a whole stride
+static size_t strided_bytes(int64_t n, int64_t nbytes, int64_t row_stride) {
+    return n > 0 ? (size_t)(n - 1) * (size_t)row_stride + (size_t)nbytes : 0;
+}
+
 template <bool HAS_VEC>
 static int launch_arr_vec(const uint8_t* arr, int64_t n, int64_t nbytes, int64_t stride,
                           const uint8_t* vec, const uint32_t* card, double* sim, uint32_t* inter,
@@ -359,7 +364,7 @@ extern "C" int bbh_popcount_rows(const uint8_t* arr, int64_t n, int64_t nbytes, 
     hipStream_t s = (hipStream_t)stream;
     bb::DevIn a;
     bb::DevOut o;
-    BB_TRY(a.init(arr, (size_t)(n * row_stride), s));
+    BB_TRY(a.init(arr, strided_bytes(n, nbytes, row_stride), s));
     BB_TRY(o.init(out, (size_t)n * 4));
     {
         bb::ProfScope ps("popcount_rows", s);
@@ -380,7 +385,7 @@ extern "C" int bbh_jt_arr_vec(const uint8_t* arr, int64_t n, int64_t nbytes, int
     hipStream_t s = (hipStream_t)stream;
     bb::DevIn a, v, c;
     bb::DevOut os, oi, ou;
-    BB_TRY(a.init(arr, (size_t)(n * row_stride), s));
+    BB_TRY(a.init(arr, strided_bytes(n, nbytes, row_stride), s));
     BB_TRY(v.init(vec, (size_t)nbytes, s));
     BB_TRY(c.init(card, card ? (size_t)n * 4 : 0, s));
     BB_TRY(os.init(out_sim, (size_t)n * 8));
@@ -437,7 +442,7 @@ __global__ __launch_bounds__(256) void k_best_match(const uint32_t* __restrict__
         for (int w = 0; w < W32; ++w) inter += __popc(x[w] & cr[w]);
         uint32_t un = qc + ccard[m] - inter;
         uint32_t unc = un < 1u ? 1u : un;
-        // inter/unc > best_i/best_u  <=>  inter*best_u > best_i*unc (exact; <= 2^26)
+        // inter/unc > best_i/best_u  <=>  inter*best_u > best_i*unc (exact in 32 bits: this kernel is 2048-bit rows only, <= 2^26)
         if (m == 0 || inter * best_u > best_i * unc) {
             best_i = inter;
             best_u = unc;
@@ -478,7 +483,9 @@ __global__ __launch_bounds__(256) void k_best_match_generic(const uint8_t* __res
         inter = wave_sum_u32(inter);
         uint32_t un = qc + ccard[m] - inter;
         uint32_t unc = un < 1u ? 1u : un;
-        if (m == 0 || inter * best_u > best_i * unc) {
+        // any width: counts go up to nbytes * 8 (2^16 at 8192 bytes a row), so the products pass 2^32 and are taken in 64 bits
+        // (the product of two uint32 counts always fits: exact at every width whose counts fit their uint32 counters)
+        if (m == 0 || (unsigned long long)inter * best_u > (unsigned long long)best_i * unc) {
             best_i = inter;
             best_u = unc;
             best_true_u = un;
@@ -871,7 +878,9 @@ extern "C" int bbh_isim_pair_min_gap(const uint64_t* sums, const uint64_t* sizes
     const unsigned long long* hsums = nullptr;
     if (bb::is_device_ptr(sums)) {
         hs.resize((size_t)k * (size_t)n_features);
-        BB_HIP(hipMemcpy(hs.data(), sums, hs.size() * 8, hipMemcpyDeviceToHost));
+        // on `stream` like every other transfer of this call: a plain hipMemcpy does not wait for a non-blocking stream
+        BB_HIP(hipMemcpyAsync(hs.data(), sums, hs.size() * 8, hipMemcpyDeviceToHost, s));
+        BB_HIP(hipStreamSynchronize(s));
         hsums = hs.data();
     } else {
         hsums = (const unsigned long long*)sums;

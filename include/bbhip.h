@@ -64,7 +64,8 @@ int bbh_set_memory_pressure_callback(void (*fn)(void));
 /* ---------------------------------------------------------------------------------- */
 
 /* _popcount_2d (similarity.cpp:99-141) and _popcount_1d (:63-94, n = 1).
- * arr: n rows x nbytes; out: n uint32. */
+ * arr: n rows x nbytes, row_stride bytes apart (>= nbytes); the last row needs only nbytes bytes, so a view that
+ * ends where its buffer ends is fine.  out: n uint32. */
 int bbh_popcount_rows(const uint8_t* arr, int64_t n, int64_t nbytes, int64_t row_stride,
                       uint32_t* out, void* stream);
 
@@ -72,6 +73,7 @@ int bbh_popcount_rows(const uint8_t* arr, int64_t n, int64_t nbytes, int64_t row
  * (:340-372) + _calc_arr_vec_jt (:304-333):
  *   out_sim[i] = inter_i / max(double(card_i + popcount(vec) - inter_i), 1.0)
  * card: optional precomputed row popcounts (NULL -> computed in the same pass).
+ * arr: rows row_stride bytes apart (>= nbytes); the last row needs only nbytes bytes.
  * out_inter / out_union: optional exact integer numerators / denominators (uint32). */
 int bbh_jt_arr_vec(const uint8_t* arr, int64_t n, int64_t nbytes, int64_t row_stride,
                    const uint8_t* vec, const uint32_t* card, double* out_sim,
@@ -81,7 +83,9 @@ int bbh_jt_arr_vec(const uint8_t* arr, int64_t n, int64_t nbytes, int64_t row_st
  * Tanimoto against nc centroid rows (np.argmax at bitbirch.py:320 fused with the
  * similarity call at :317).  out_idx: nq int32; out_inter/out_union: optional nq uint32
  * of the winning pair; out_sims: optional nq x nc float64 full matrix
- * (jt_sim_matrix_packed, similarity.py:239-247, when queries == centroids). */
+ * (jt_sim_matrix_packed, similarity.py:239-247, when queries == centroids).
+ * Any nbytes: the comparison is an exact integer cross-multiplication at every row width (64-bit products where
+ * the counts need them), never a comparison of rounded quotients. */
 int bbh_jt_best_match(const uint8_t* queries, int64_t nq, const uint8_t* cents, int64_t nc,
                       int64_t nbytes, int32_t* out_idx, uint32_t* out_inter,
                       uint32_t* out_union, double* out_sims, void* stream);
