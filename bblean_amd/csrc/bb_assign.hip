@@ -256,7 +256,8 @@ __global__ __launch_bounds__(256) void k_assign_mfma(const uint8_t* __restrict__
                     const int inter = acc[mt][nt][r];
                     const int un = qc[nt] + cc - inter;
                     const int n = inter + (un == 0 ? 1 : 0);
-                    // (n <= 2049, u <= 6144: the products fit 24 bits)
+                    // (__mul24 multiplies the low 24 bits of its operands, signed: n <= 2049 and u <= 6144 fit, -1 included;
+                    //  the products, up to 2049 * 6144 < 2^24, fit the 32 bits it returns)
                     if (__mul24(n, best[nt].u) > __mul24(best[nt].n, un)) best[nt] = Cand{n, un, m};
                 }
             }

@@ -309,3 +309,155 @@ def ref_most_dissimilar(Y: np.ndarray, nf: int):
 def bits(x: np.ndarray) -> np.ndarray:
     r"""float64 -> its uint64 bit patterns (comparisons are on these: -0.0 != 0.0, NaN == the same NaN)."""
     return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# assignment (bblean_amd/csrc/bb_assign.hip): reference, case lists and builders of test_hip_assign_edges.py
+# ---------------------------------------------------------------------------------------------------------------------
+
+
+def exact(q: np.ndarray, c: np.ndarray):
+    r"""(first argmin, its intersection, its union, the distance matrix) from exact integer counts."""
+    qb = np.unpackbits(q, axis=1).astype(np.float32)  # 0/1 sums <= 2^24: exact in float32
+    cb = np.unpackbits(c, axis=1).astype(np.float32)
+    inter = (qb @ cb.T).astype(np.int64)
+    union = qb.sum(1).astype(np.int64)[:, None] + cb.sum(1).astype(np.int64)[None, :] - inter
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = np.where(union == 0, 0.0, (union - inter).astype(np.float64) / union.astype(np.float64))
+    idx = np.argmin(d, axis=1)  # equal fractions divide to the same double: float64 ties are the rational ties
+    r = np.arange(q.shape[0])
+    return idx.astype(np.int32), inter[r, idx].astype(np.uint32), union[r, idx].astype(np.uint32), d
+
+
+def density_rows(rng: np.random.Generator, n: int, nb: int, lo: float, hi: float) -> np.ndarray:
+    r"""n packed rows, each at its own bit density from [lo, hi]."""
+    return np.packbits(rng.random((n, nb * 8)) < rng.uniform(lo, hi, (n, 1)), axis=1)
+
+
+# the widths k_assign_bcnt / k_jaccard_dist are instantiated for (bb_assign.hip: W32 = nbytes / 4)
+ASSIGN_FAST_WIDTHS = (8, 16, 32, 64, 128, 256)
+ASSIGN_SHAPES = ((1, 1), (255, 65), (256, 64), (257, 63), (513, 700))
+ASSIGN_WIDTH_CASES = [(nb, nq, nc) for nb in ASSIGN_FAST_WIDTHS for nq, nc in ASSIGN_SHAPES]
+ASSIGN_DISPATCH_CASES = [(256, 63, 64), (256, 64, 63), (256, 64, 64)]  # use_mfma needs nq >= 64 and nc >= 64
+
+
+def assign_inputs(nb: int, nq: int, nc: int) -> tuple[np.ndarray, np.ndarray]:
+    r"""Rows of up to 16 bytes at density 1/2 (exact ties are common), wider ones at 0.05 .. 0.3; an all-zero query and an
+    all-zero centroid where there is room; at 8, 64 and 256 bytes (1, 1) is the all-zero query against the all-zero centroid."""
+    rng = np.random.default_rng([31, nb, nq, nc])
+    if nb <= 16:
+        q, c = (rng.integers(0, 256, (n, nb), dtype=np.uint8) for n in (nq, nc))
+    else:
+        q, c = density_rows(rng, nq, nb, 0.05, 0.3), density_rows(rng, nc, nb, 0.05, 0.3)
+    if nq > 2:
+        q[nq // 2] = 0
+    if nc > 3:
+        c[nc // 3] = 0
+    if (nq, nc) == (1, 1) and nb in (8, 64, 256):
+        q[:], c[:] = 0, 0
+    return q, c
+
+
+# device layouts of the alignment cases: name -> (query base offset, centroid base offset, q_stride - nbytes or None for 2 x)
+ASSIGN_LAYOUTS = {
+    "q+4": (4, 0, 0), "c+4": (0, 4, 0), "both+4": (4, 4, 0), "q+1": (1, 0, 0), "both+1": (1, 1, 0),
+    "stride+4": (0, 0, 4), "stride+1": (0, 0, 1), "stride x2": (0, 0, None),
+}
+ASSIGN_ALIGN_SHAPE = (300, 130)  # both >= 64: the aligned 256-byte call goes to the matrix cores on its own
+
+
+def layout_stride(name: str, nb: int) -> int:
+    extra = ASSIGN_LAYOUTS[name][2]
+    return 2 * nb if extra is None else nb + extra
+
+
+def strided_buffer(rows: np.ndarray, off: int, stride: int) -> np.ndarray:
+    r"""A flat buffer of 0xFF with rows[i] at off + i * stride that ends with the last row's last byte."""
+    n, nb = rows.shape
+    flat = np.full(off + (n - 1) * stride + nb, 0xFF, np.uint8)
+    np.lib.stride_tricks.as_strided(flat[off:], (n, nb), (stride, 1))[:] = rows
+    return flat
+
+
+# distance matrix: several queries per grid range (k_jaccard_dist's inner loop), as bbh_jt_dist_matrix cuts them
+DIST_RANGE_CASES = [(16, 5000, 300), (16, 4097, 257), (16, 5003, 300)]
+DIST_GRID_Z_CASE = (3, 65535 + 70, 3)  # generic kernel, the second turn of blockIdx.z
+
+
+def dist_queries_per_range(nq: int, nc: int, cus: int) -> int:
+    cblocks = (nc + 255) // 256
+    want = min((4 * cus + cblocks - 1) // cblocks, nq, 65535)
+    return (nq + want - 1) // want
+
+
+ASSIGN_WIDE_WIDTHS = (8192, 8200)
+ASSIGN_WIDE_SHAPE = (6, 40)
+
+
+def assign_wide_inputs(nb: int) -> tuple[np.ndarray, np.ndarray]:
+    r"""65 536-bit rows and a little more, dense: n * u passes 2^32.  q[0] / c[0], c[1] are best_match_overflow_inputs (all
+    ones against all ones but one bit, then all ones: index 1); c[7] = c[5] is q[2]'s nearest, the first of the two wins."""
+    rng = np.random.default_rng([32, nb])
+    nq, nc = ASSIGN_WIDE_SHAPE
+    q, c = density_rows(rng, nq, nb, 0.7, 0.95), density_rows(rng, nc, nb, 0.7, 0.95)
+    oq, oc = best_match_overflow_inputs()
+    q[0], c[:2] = 0xFF, 0xFF
+    q[0, :8192], c[:2, :8192] = oq[0], oc
+    c[7] = c[5]
+    q[2] = c[5] & density_rows(rng, 1, nb, 0.9, 0.9)[0]
+    q[5] = 0xFF
+    c[20] = 0
+    return q, c
+
+
+def first_argmin_int32(inter: np.ndarray, union: np.ndarray) -> int:
+    r"""k_assign_generic's scan with the cross-multiplication wrapped to a signed 32-bit integer."""
+    def wrap(v):
+        v &= 0xFFFFFFFF
+        return v - (1 << 32) if v >= 1 << 31 else v
+    bn, bu, best = -1, 1, 0
+    for m in range(len(inter)):
+        u = int(union[m])
+        n = int(inter[m]) + (u == 0)
+        if wrap(n * bu) > wrap(bn * u):
+            bn, bu, best = n, u, m
+    return best
+
+
+# matrix cores at their limits: 256-byte rows, nc so that padded rows sit in every lane group and in a whole wave half
+MFMA_LIMIT_NCS = (1, 65, 129)
+MFMA_LIMIT_NQ = 130
+
+
+def mfma_limit_inputs(nc: int) -> tuple[np.ndarray, np.ndarray]:
+    r"""All-ones, all-zero and dense (0.5, 0.9) rows on both sides."""
+    rng = np.random.default_rng([33, nc])
+
+    def side(n):
+        x = np.concatenate([density_rows(rng, n - n // 2, 256, 0.5, 0.5), density_rows(rng, n // 2, 256, 0.9, 0.9)])
+        rng.shuffle(x)
+        x[0] = 0xFF
+        if n > 2:
+            x[n // 2] = 0
+            x[n - 1] = 0xFF
+        return x
+    return side(MFMA_LIMIT_NQ), side(nc)
+
+
+ONE_HOT_WIDTHS = (32, 64, 128, 256)
+
+
+def one_hot_inputs(nb: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    r"""(queries = the nb * 8 one-hot rows, centroids = the same rows permuted + one all-ones row, position of query j's
+    own centroid).  A kernel that takes the two operands through different orders of the bits pairs a query with the wrong one-hot
+    centroid: intersection 0 where (1, 1) is expected."""
+    n = nb * 8
+    q = np.packbits(np.eye(n, dtype=np.uint8), axis=1)
+    perm = np.random.default_rng([34, nb]).permutation(n)
+    c = np.concatenate([q[perm], np.full((1, nb), 0xFF, np.uint8)])
+    where = np.empty(n, np.int32)
+    where[perm] = np.arange(n, dtype=np.int32)
+    return q, c, where
+
+
+ASSIGN_OUTPUT_CASES = [(256, 200, 150), (16, 300, 70), (100, 70, 70)]  # matrix cores, popcount, generic

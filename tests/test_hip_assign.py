@@ -10,6 +10,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from kernel_refs import exact
 from sklearn_cases import CASES, rows
 
 pytestmark = pytest.mark.gpu
@@ -35,19 +36,6 @@ def forced(mode):
 
 def modes_for(nbytes):
     return MODES if nbytes == 256 else (None, "bcnt")
-
-
-def exact(q, c):
-    r"""(first argmin, its intersection, its union, the distance matrix) from exact integer counts."""
-    qb = np.unpackbits(q, axis=1).astype(np.float32)  # 0/1 sums <= 2^24: exact in float32
-    cb = np.unpackbits(c, axis=1).astype(np.float32)
-    inter = (qb @ cb.T).astype(np.int64)
-    union = qb.sum(1).astype(np.int64)[:, None] + cb.sum(1).astype(np.int64)[None, :] - inter
-    with np.errstate(invalid="ignore", divide="ignore"):
-        d = np.where(union == 0, 0.0, (union - inter).astype(np.float64) / union.astype(np.float64))
-    idx = np.argmin(d, axis=1)  # equal fractions divide to the same double: float64 ties are the rational ties
-    r = np.arange(q.shape[0])
-    return idx.astype(np.int32), inter[r, idx].astype(np.uint32), union[r, idx].astype(np.uint32), d
 
 
 def check(q, c, what=""):

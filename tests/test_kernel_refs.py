@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import kernel_refs as R
+import medoid_cases as mc
 from oracle_engine import oracle_lib
 
 
@@ -215,3 +216,145 @@ def test_ref_pair_min_gap(k, f):
     assert R.ref_pair_min_gap(sums, sizes) == best
     if (k, f) == (2, 8):
         assert best == 0.0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# assignment: kernel_refs.exact against the oracle's counts, on the case lists of test_hip_assign_edges.py
+# ---------------------------------------------------------------------------------------------------------------------
+
+
+def assert_exact_is_the_oracles(q, c):
+    r"""Per query: the distance row is (u - i) / u of the oracle's counts (0.0 for an empty union), no centroid is nearer than
+    exact()'s index by exact cross-multiplication, none before it is as near, and its counts are the oracle's."""
+    idx, inter, union, d = R.exact(q, c)
+    for k in range(len(q)):
+        _, i, u = o_arr_vec(c, q[k])
+        i, u = i.astype(np.int64), u.astype(np.int64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            want = np.where(u == 0, 0.0, (u - i).astype(np.float64) / u.astype(np.float64))
+        assert (R.bits(d[k]) == R.bits(want)).all()
+        b = int(idx[k])
+        assert (int(inter[k]), int(union[k])) == (int(i[b]), int(u[b]))
+        n = i + (u == 0)  # an empty union is (1, 0): nearer than everything
+        left, right = n * u[b], n[b] * u  # < 2^63 for rows of up to 2^31 bits
+        assert not (left > right).any() and int(np.argmax(left == right)) == b
+
+
+ASSIGN_CPU_CASES = [c for c in R.ASSIGN_WIDTH_CASES if c[1] <= 257] + [(16, 513, 700), (256, 513, 700)] + R.ASSIGN_DISPATCH_CASES
+
+
+@pytest.mark.parametrize("nb,nq,nc", ASSIGN_CPU_CASES)
+def test_exact_on_the_width_cases(nb, nq, nc):
+    q, c = R.assign_inputs(nb, nq, nc)
+    assert_exact_is_the_oracles(q, c)
+    if nb <= 16 and nq > 200:  # density 1/2 on narrow rows: exact ties between different centroids occur
+        d = R.exact(q, c)[3]
+        assert ((d == d.min(axis=1, keepdims=True)).sum(axis=1) > 1).any()
+
+
+@pytest.mark.parametrize("nb", R.ASSIGN_WIDE_WIDTHS)
+def test_exact_on_wide_rows(nb):
+    r"""... and a scan that multiplies in 32 bits goes wrong on them."""
+    q, c = R.assign_wide_inputs(nb)
+    assert_exact_is_the_oracles(q, c)
+    idx = R.exact(q, c)[0]
+    wrong = 0
+    for k in range(len(q)):
+        _, i, u = o_arr_vec(c, q[k])
+        wrong += R.first_argmin_int32(i, u) != idx[k]
+    assert wrong > 0
+
+
+@pytest.mark.parametrize("nc", R.MFMA_LIMIT_NCS)
+def test_exact_on_the_matrix_core_limits(nc):
+    q, c = R.mfma_limit_inputs(nc)
+    assert_exact_is_the_oracles(q, c)
+    assert {0, 2048} <= set(R.ref_popcount(q).tolist()) and 2048 in R.ref_popcount(c).tolist()
+
+
+@pytest.mark.parametrize("nb", [w for w in R.ONE_HOT_WIDTHS if w <= 128])
+def test_exact_on_one_hot_rows(nb):
+    q, c, where = R.one_hot_inputs(nb)
+    assert_exact_is_the_oracles(q, c)
+    idx, inter, union, _ = R.exact(q, c)
+    assert (idx == where).all() and (inter == 1).all() and (union == 1).all()
+    assert (c[where] == q).all()
+
+
+def test_strided_buffer_and_ranges():
+    q = R.assign_inputs(16, 7, 5)[0]
+    for name in R.ASSIGN_LAYOUTS:
+        off, stride = R.ASSIGN_LAYOUTS[name][0], R.layout_stride(name, 16)
+        flat = R.strided_buffer(q, off, stride)
+        assert flat.nbytes == off + 6 * stride + 16
+        assert all((flat[off + i * stride: off + i * stride + 16] == q[i]).all() for i in range(7))
+        assert (flat[:off] == 0xFF).all() and (stride == 16 or (flat[off + 16: off + stride] == 0xFF).all())
+    # the MI355X has 256 compute units
+    assert [R.dist_queries_per_range(nq, nc, 256) for _, nq, nc in R.DIST_RANGE_CASES] == [10, 9, 10]
+    assert [nq % R.dist_queries_per_range(nq, nc, 256) for _, nq, nc in R.DIST_RANGE_CASES] == [0, 2, 3]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# medoids: the weighted reference of medoid_cases.py against the per-row one and against the reference's own values
+# ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("nf_short", [False, True])
+@pytest.mark.parametrize("nb", [8, 260, 516])
+@pytest.mark.parametrize("m", [1, 2, 3, 40, 3000])
+def test_weighted_is_the_expanded_set(m, nb, nf_short):
+    rng = np.random.default_rng([50, m, nb])
+    distinct = np.packbits(rng.random((20, nb * 8)) < rng.uniform(0.05, 0.9, (20, 1)), axis=1)
+    distinct[3] = 0
+    distinct[4] = 0xFF
+    mem = rng.integers(0, 20, m)
+    nf = nb * 8 - 16 if nf_short else None
+    values = mc.compl_isim_weighted(distinct, np.bincount(mem, minlength=20), nf)
+    want = mc.compl_isim_set(distinct[mem], nf)
+    assert values.shape == (20,)
+    if m < 3:
+        assert np.isnan(values).all() and np.isnan(want).all()
+        return
+    assert (R.bits(values[mem]) == R.bits(want)).all()
+    assert mc.weighted_medoid(values, mem) == int(np.argmin(want))
+
+
+def test_weighted_is_the_references_big_set():
+    from pathlib import Path
+
+    from bblean_amd.fingerprints import make_fake_fingerprints
+
+    gold = np.load(Path(__file__).resolve().parent / "golden" / "medoids.npz")
+    distinct, draw = mc.big_rows(make_fake_fingerprints)
+    counts = np.bincount(draw, minlength=len(distinct))
+    assert counts.min() > 0
+    values = mc.compl_isim_weighted(distinct, counts)
+    assert (R.bits(values) == R.bits(gold["big_compl_distinct"])).all()
+    assert mc.weighted_medoid(values, draw) == int(gold["big_medoid"].reshape(-1)[0])
+
+
+@pytest.mark.parametrize("m,nb,with_zero", [c for c in mc.PLANE_CASES if c[0] <= 1 << 20])
+def test_plane_cases_select_their_instances(m, nb, with_zero):
+    distinct, mem = mc.plane_distinct(nb), mc.plane_members(m, nb, with_zero)
+    assert len(mem) == m and mem.min() == (0 if with_zero else 1) and mem.max() == 47
+    kernel, wpl, planes = mc.instance_of(m, nb)
+    assert kernel == ("wide" if nb == 516 else "rows") and (nb == 516 or (wpl, planes) == (1 if nb == 8 else 2, mc.PLANE_EXPECT[m]))
+    ls = mc.column_sums(distinct, np.bincount(mem, minlength=48))
+    assert int(ls[0]) == m - int((mem == 0).sum())
+    for lo in (0, mc.FULL_CHUNK * mc.CHUNK):  # chunks whose count of the shared column is exactly 256
+        assert (distinct[mem[lo:lo + mc.CHUNK], 0] & mc.SHARED_BIT).all()
+
+
+def test_plane_instances_are_all_there():
+    got = {mc.instance_of(m, nb) for m, nb, _ in mc.PLANE_CASES}
+    assert {("rows", w, p) for w in (1, 2) for p in (16, 20, 24, 32)} - got == {("rows", 2, 16), ("rows", 2, 32)}
+    assert {("wide", 0, 17), ("wide", 0, 21)} <= got
+    # <2, 16> runs in tests/test_hip_medoid.py and in the word-boundary cases; <2, 32> needs 2^24 rows of more than 256 bytes
+    assert mc.instance_of(5000, 260) == ("rows", 2, 16)
+
+
+@pytest.mark.parametrize("first", mc.ARGMIN_FIRST)
+def test_argmin_cases_put_the_first_copy_where_they_say(first):
+    distinct, mem, r0 = mc.argmin_case(first)
+    values = mc.compl_isim_weighted(distinct, np.bincount(mem, minlength=len(distinct)))
+    assert np.flatnonzero(values == values.min()).tolist() == [r0]
+    assert int(np.flatnonzero(mem == r0)[0]) == first == mc.weighted_medoid(values, mem)
