@@ -2752,18 +2752,20 @@ int init_empty(bbh_tree* t) {
 }
 
 int set_tol(bbh_tree* t, const double* tab, int64_t len) {
-    if (t->d_tol) {
-        (void)bb::dev_free(t->d_tol);
-        t->d_tol = nullptr;
-    }
-    t->h.tol_table = nullptr;
-    t->h.tol_len = 0;
+    // the new table is complete on the device before the old one is let go: a failure leaves the tree with the old table
+    double* fresh = nullptr;
     if (tab && len > 0) {
-        BB_HIP(bb::dev_alloc(&t->d_tol, (size_t)len * 8));
-        BB_HIP(hipMemcpy(t->d_tol, tab, (size_t)len * 8, hipMemcpyHostToDevice));
-        t->h.tol_table = t->d_tol;
-        t->h.tol_len = (int32_t)len;
+        BB_HIP(bb::dev_alloc(&fresh, (size_t)len * 8));
+        const hipError_t e = hipMemcpy(fresh, tab, (size_t)len * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)bb::dev_free(fresh);
+            BB_HIP(e);
+        }
     }
+    if (t->d_tol) (void)bb::dev_free(t->d_tol);
+    t->d_tol = fresh;
+    t->h.tol_table = fresh;
+    t->h.tol_len = fresh ? (int32_t)len : 0;
     return BBH_OK;
 }
 
@@ -3682,16 +3684,20 @@ extern "C" int bbh_tree_set_merge(bbh_tree* t, int32_t criterion, double toleran
                                   int64_t tol_len, double threshold, int32_t branching_factor) {
     if (!t) return bb::fail(BBH_ERR_INVALID, "null tree");
     if (criterion < 0 || criterion > BBH_CRIT_NEVER) return bb::fail(BBH_ERR_INVALID, "unknown merge criterion %d", criterion);
-    t->h.crit = criterion;
-    t->h.tolerance = tolerance;
-    t->h.thr = threshold;
-    BB_TRY(set_tol(t, tol_table, tol_len));
+    // every refusal comes before the first change: a call that returns an error leaves the tree as it was
     if (branching_factor != t->h.bf) {
+        if (branching_factor < 2 || branching_factor > MAX_BF)
+            return bb::fail(BBH_ERR_INVALID, "branching_factor must be in [2, %d]", MAX_BF);
         const bool empty = t->h.ctr[C_NODES] == node_blocks((uint32_t)t->h.bf + 1) && t->h.ctr[C_IDS] == 0;
         if (!empty)
             return bb::fail(BBH_ERR_STATE, "branching_factor can only change on an empty tree: call reset() first");
-        if (branching_factor < 2 || branching_factor > MAX_BF)
-            return bb::fail(BBH_ERR_INVALID, "branching_factor must be in [2, %d]", MAX_BF);
+    }
+    BB_HIP(hipSetDevice(t->device));
+    BB_TRY(set_tol(t, tol_table, tol_len));
+    t->h.crit = criterion;
+    t->h.tolerance = tolerance;
+    t->h.thr = threshold;
+    if (branching_factor != t->h.bf) {
         free_pools(t);
         BB_TRY(configure(t, branching_factor, t->h.F));
         BB_TRY(init_empty(t));
@@ -3717,7 +3723,8 @@ struct HostSlabs {
     static constexpr size_t kSlabBytes = 64ull << 20;
     int device = 0;
     const uint8_t* src = nullptr;
-    size_t unit = 0;           // bytes per row (stride)
+    size_t unit = 0;           // bytes from one row to the next (stride)
+    size_t row = 0;            // bytes of a row: the last row of the source needs only these
     int64_t total = 0, per = 0;  // rows in all / per slab
     uint8_t* pin[2] = {nullptr, nullptr};
     uint8_t* dev[2] = {nullptr, nullptr};
@@ -3725,8 +3732,8 @@ struct HostSlabs {
     std::future<int> pending;
     int64_t next = 0;  // first row of the slab being fetched
 
-    int init(int device_, const void* src_, size_t unit_, int64_t total_) {
-        device = device_; src = (const uint8_t*)src_; unit = unit_; total = total_;
+    int init(int device_, const void* src_, size_t unit_, size_t row_, int64_t total_) {
+        device = device_; src = (const uint8_t*)src_; unit = unit_; row = row_; total = total_;
         size_t slab_bytes = kSlabBytes;
         if (const char* e = getenv("BBHIP_SLAB_KB")) slab_bytes = std::max<size_t>(1, (size_t)atoll(e)) << 10;  // tests
         per = std::max<int64_t>(1, (int64_t)(slab_bytes / unit));
@@ -3746,8 +3753,10 @@ struct HostSlabs {
         const int64_t m = std::min(per, total - first);
         auto job = [this, b, first, m]() -> int {
             if (hipSetDevice(device) != hipSuccess) return 1;
-            std::memcpy(pin[b], src + (size_t)first * unit, (size_t)m * unit);  // page-in happens here
-            if (hipMemcpyAsync(dev[b], pin[b], (size_t)m * unit, hipMemcpyHostToDevice, cs) != hipSuccess) return 2;
+            // (m - 1) strides and one row: a strided view may end where its buffer ends
+            const size_t bytes = (size_t)(m - 1) * unit + row;
+            std::memcpy(pin[b], src + (size_t)first * unit, bytes);  // page-in happens here
+            if (hipMemcpyAsync(dev[b], pin[b], bytes, hipMemcpyHostToDevice, cs) != hipSuccess) return 2;
             return hipStreamSynchronize(cs) == hipSuccess ? 0 : 3;
         };
         try {
@@ -3782,6 +3791,7 @@ extern "C" int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, 
     if (!t) return bb::fail(BBH_ERR_INVALID, "null tree");
     if (n < 0 || row_stride < t->h.nbytes) return bb::fail(BBH_ERR_INVALID, "rows must be (n, n_features/8) uint8");
     if (n == 0) return BBH_OK;
+    if (!rows) return bb::fail(BBH_ERR_INVALID, "null rows with n > 0");
     BB_HIP(hipSetDevice(t->device));
     hipStream_t s = (hipStream_t)stream;
     BB_TRY(pregrow(t, n, 0));
@@ -3791,7 +3801,7 @@ extern "C" int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, 
         BB_TRY(run_insert(t, rows, row_stride, nullptr, 0, n, (uint32_t*)o.dev, s));
     } else {
         HostSlabs slabs;
-        BB_TRY(slabs.init(t->device, rows, (size_t)row_stride, n));
+        BB_TRY(slabs.init(t->device, rows, (size_t)row_stride, (size_t)t->h.nbytes, n));
         for (int64_t off = 0; off < n;) {
             const uint8_t* d = nullptr;
             int64_t m = 0;
@@ -3867,6 +3877,7 @@ extern "C" int bbh_tree_fit_buffers(bbh_tree* t, const void* bufs, int32_t width
     if (width != 1 && width != 2 && width != 4 && width != 8) return bb::fail(BBH_ERR_INVALID, "buffer element width must be 1, 2, 4 or 8");
     if (k < 0) return bb::fail(BBH_ERR_INVALID, "negative buffer count");
     if (k == 0) return BBH_OK;
+    if (!bufs) return bb::fail(BBH_ERR_INVALID, "null buffers with k > 0");
     BB_HIP(hipSetDevice(t->device));
     hipStream_t s = (hipStream_t)stream;
     BB_TRY(pregrow(t, k, width));
@@ -3894,7 +3905,7 @@ extern "C" int bbh_tree_fit_buffers(bbh_tree* t, const void* bufs, int32_t width
         }
     } else {
         HostSlabs slabs;
-        BB_TRY(slabs.init(t->device, bufs, row_bytes, k));
+        BB_TRY(slabs.init(t->device, bufs, row_bytes, row_bytes, k));
         std::vector<uint8_t> n_col;
         for (int64_t off = 0; off < k;) {
             const uint8_t* d = nullptr;
@@ -3926,15 +3937,22 @@ extern "C" int bbh_trees_fit_packed(bbh_tree** trees, int32_t n_trees, const uin
     std::vector<Job> jobs;
     std::vector<bb::DevIn> ins((size_t)n_trees);
     std::vector<bb::DevOut> outs((size_t)n_trees);
+    // every argument is checked before the first tree is touched
+    for (int32_t i = 0; i < n_trees; ++i) {
+        const bbh_tree* t = trees[i];
+        if (!t) return bb::fail(BBH_ERR_INVALID, "null tree at index %d", i);
+        if (t->device != trees[0]->device) return bb::fail(BBH_ERR_INVALID, "all trees of one call must live on one device");
+        if (n[i] < 0 || row_stride[i] < t->h.nbytes) return bb::fail(BBH_ERR_INVALID, "rows must be (n, n_features/8) uint8");
+        if (n[i] > 0 && !rows[i]) return bb::fail(BBH_ERR_INVALID, "null rows with n > 0 at index %d", i);
+    }
     const int device = trees[0]->device;
     BB_HIP(hipSetDevice(device));
     for (int32_t i = 0; i < n_trees; ++i) {
         bbh_tree* t = trees[i];
-        if (!t || t->device != device) return bb::fail(BBH_ERR_INVALID, "all trees of one call must live on one device");
-        if (n[i] < 0 || row_stride[i] < t->h.nbytes) return bb::fail(BBH_ERR_INVALID, "rows must be (n, n_features/8) uint8");
         if (n[i] == 0) continue;
         BB_TRY(pregrow(t, n[i], 0));
-        BB_TRY(ins[(size_t)i].init(rows[i], (size_t)(n[i] * row_stride[i]), s));
+        // (n - 1) strides and one row: a strided host view may end where its buffer ends
+        BB_TRY(ins[(size_t)i].init(rows[i], (size_t)(n[i] - 1) * (size_t)row_stride[i] + (size_t)t->h.nbytes, s));
         BB_TRY(outs[(size_t)i].init(out_leaf ? out_leaf[i] : nullptr, (size_t)n[i] * 4));
         jobs.push_back(Job{t, (const uint8_t*)ins[(size_t)i].dev, row_stride[i], nullptr, 0, n[i],
                            (uint32_t*)outs[(size_t)i].dev, 0, 0});
@@ -3955,14 +3973,21 @@ extern "C" int bbh_trees_fit_buffers(bbh_tree** trees, int32_t n_trees, const vo
     std::vector<Job> jobs;
     std::vector<bb::DevIn> ins((size_t)n_trees);
     std::vector<bb::DevOut> outs((size_t)n_trees);
+    // every argument is checked before the first tree is touched
+    for (int32_t i = 0; i < n_trees; ++i) {
+        const bbh_tree* t = trees[i];
+        if (!t) return bb::fail(BBH_ERR_INVALID, "null tree at index %d", i);
+        if (t->device != trees[0]->device) return bb::fail(BBH_ERR_INVALID, "all trees of one call must live on one device");
+        const int w = width[i];
+        if (w != 1 && w != 2 && w != 4 && w != 8) return bb::fail(BBH_ERR_INVALID, "buffer element width must be 1, 2, 4 or 8");
+        if (k[i] < 0) return bb::fail(BBH_ERR_INVALID, "negative buffer count");
+        if (k[i] > 0 && !bufs[i]) return bb::fail(BBH_ERR_INVALID, "null buffers with k > 0 at index %d", i);
+    }
     const int device = trees[0]->device;
     BB_HIP(hipSetDevice(device));
     for (int32_t i = 0; i < n_trees; ++i) {
         bbh_tree* t = trees[i];
-        if (!t || t->device != device) return bb::fail(BBH_ERR_INVALID, "all trees of one call must live on one device");
         const int w = width[i];
-        if (w != 1 && w != 2 && w != 4 && w != 8) return bb::fail(BBH_ERR_INVALID, "buffer element width must be 1, 2, 4 or 8");
-        if (k[i] < 0) return bb::fail(BBH_ERR_INVALID, "negative buffer count");
         if (k[i] == 0) continue;
         BB_TRY(pregrow(t, k[i], w));
         const size_t row_bytes = ((size_t)t->h.F + 1) * (size_t)w;
@@ -4055,6 +4080,7 @@ static int gather_positions(bbh_tree* t, const int64_t* positions, int64_t m, in
 
 extern "C" int bbh_tree_gather_buffers(bbh_tree* t, const int64_t* positions, int64_t m, int32_t width, void* out) {
     if (!t || (m > 0 && (!positions || !out))) return bb::fail(BBH_ERR_INVALID, "null argument");
+    if (m < 0) return bb::fail(BBH_ERR_INVALID, "negative position count");
     if (width != 1 && width != 2 && width != 4 && width != 8) return bb::fail(BBH_ERR_INVALID, "width must be 1, 2, 4 or 8");
     if (m == 0) return BBH_OK;
     return gather_positions(t, positions, m, width, out, nullptr);
@@ -4062,6 +4088,7 @@ extern "C" int bbh_tree_gather_buffers(bbh_tree* t, const int64_t* positions, in
 
 extern "C" int bbh_tree_gather_centroids(bbh_tree* t, const int64_t* positions, int64_t m, uint8_t* out) {
     if (!t || (m > 0 && (!positions || !out))) return bb::fail(BBH_ERR_INVALID, "null argument");
+    if (m < 0) return bb::fail(BBH_ERR_INVALID, "negative position count");
     if (m == 0) return BBH_OK;
     return gather_positions(t, positions, m, 0, nullptr, out);
 }

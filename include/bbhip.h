@@ -178,14 +178,21 @@ int bbh_most_dissimilar(const uint8_t* Y, int64_t n, int64_t nbytes, int64_t n_f
 typedef struct bbh_tree bbh_tree;
 
 /* BitBirch.__init__ (bitbirch.py:596-643).  tol_table[old_n] is the adaptive tolerance
- * of _merges.py:113 evaluated by the caller (entries >= tol_len are 0); may be NULL. */
+ * of _merges.py:113 evaluated by the caller (entries >= tol_len are 0); may be NULL.
+ * branching_factor in [2, 1023], n_features a multiple of 8 in [8, 8192]: every corner of that
+ * range runs (bf 2 and 1023 at 8 and 8192 features are tested).  *out is NULL after an error. */
 int bbh_tree_create(bbh_tree** out, int32_t branching_factor, double threshold,
                     int32_t criterion, double tolerance, const double* tol_table,
                     int64_t tol_len, int32_t n_features, int32_t device);
 int bbh_tree_destroy(bbh_tree* t);
 
 /* BitBirch.set_merge (bitbirch.py:674-703).  A branching factor change requires an
- * empty (reset) tree, which is how the reference's callers use it. */
+ * empty (never fitted or reset) tree, which is how the reference's callers use it: on any
+ * other tree it is BBH_ERR_STATE; a branching factor outside [2, 1023] or an unknown
+ * criterion is BBH_ERR_INVALID.  A call that is refused (BBH_ERR_INVALID, BBH_ERR_STATE) leaves
+ * the tree as it was: criterion, tolerance, table and threshold are only applied once nothing is
+ * refused, and the new table is on the device before the old one is released.  (A HIP error
+ * while the pools of a new branching factor are set up leaves an empty tree to be destroyed.) */
 int bbh_tree_set_merge(bbh_tree* t, int32_t criterion, double tolerance,
                        const double* tol_table, int64_t tol_len, double threshold,
                        int32_t branching_factor);
@@ -194,6 +201,9 @@ int bbh_tree_set_merge(bbh_tree* t, int32_t criterion, double tolerance,
 int bbh_tree_reset(bbh_tree* t);
 
 /* BitBirch.fit hot loop (bitbirch.py:769-787): insert n packed fingerprints in order.
+ * rows: n rows of n_features/8 bytes, row_stride bytes apart (>= n_features/8); the last row
+ * needs only nbytes bytes, so a view that ends where its buffer ends is fine.  n == 0 is
+ * BBH_OK whatever rows is; NULL rows with n > 0 are BBH_ERR_INVALID.
  * out_leaf[e] = id of the leaf BitFeature that element e was merged into or created
  * (ids are stable until reset); host or device, may be NULL.  Synchronous. */
 int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, int64_t row_stride,
@@ -201,19 +211,26 @@ int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, int64_t row
 
 /* The same for several independent trees (the shards of multiround's first round,
  * multiround.py:401-422) in ONE kernel launch, one workgroup per tree: the trees insert
- * concurrently on different compute units.  All trees must live on one device. */
+ * concurrently on different compute units.  All trees must live on one device.
+ * rows[i]: as for bbh_tree_fit_packed - the last row needs only nbytes bytes; rows[i] may be
+ * NULL where n[i] == 0 and NULL rows with n[i] > 0 are BBH_ERR_INVALID.  out_leaf, or any
+ * out_leaf[i], may be NULL.  Every argument of every tree is checked before the first tree is
+ * touched: a NULL entry of trees[] is BBH_ERR_INVALID and no tree has changed. */
 int bbh_trees_fit_packed(bbh_tree** trees, int32_t n_trees, const uint8_t* const* rows,
                          const int64_t* n, const int64_t* row_stride, uint32_t* const* out_leaf,
                          void* stream);
 /* _fit_buffers for several independent trees in one launch (the trees of a merge round,
- * multiround.py:240-264): tree i inserts k[i] buffers of element width width[i] from bufs[i]. */
+ * multiround.py:240-264): tree i inserts k[i] buffers of element width width[i] from bufs[i].
+ * NULL bufs[i] with k[i] > 0 are BBH_ERR_INVALID; checked before the first tree is touched. */
 int bbh_trees_fit_buffers(bbh_tree** trees, int32_t n_trees, const void* const* bufs,
                           const int32_t* width, const int64_t* k, uint32_t* const* out_leaf,
                           void* stream);
 
 /* BitBirch._fit_buffers hot loop (bitbirch.py:848-866): insert k BitFeature buffers
  * [linear_sum(n_features) | n_samples], elements of `width` bytes (1,2,4,8), row-major
- * with (n_features+1) columns.  Synchronous. */
+ * with (n_features+1) columns.  Synchronous.  NULL bufs with k > 0 are BBH_ERR_INVALID.
+ * n_samples >= 2^32 (a width-8 table, or a merge that would reach it) is BBH_ERR_INVALID; the
+ * tree must be reset (bbh_tree_reset) before it is used again. */
 int bbh_tree_fit_buffers(bbh_tree* t, const void* bufs, int32_t width, int64_t k,
                          uint32_t* out_leaf, void* stream);
 
@@ -223,14 +240,16 @@ int bbh_tree_leaf_count(bbh_tree* t, int64_t* out);
 /* Leaves in leaf-chain order (bitbirch.py:886-893 flattened).  Every output optional
  * (NULL); host or device.  leaf_ids: k uint32; n_samples: k uint64;
  * packed_centroids: k x ceil(F/8) uint8; linear_sums: k x F elements of ls_width bytes
- * (1,2,4,8 -- values must fit; the Python shim asks per dtype group). */
+ * (1,2,4,8 -- values must fit; the Python shim asks per dtype group.  A value that does not
+ * fit is cast, i.e. its low bits are written). */
 int bbh_tree_export_leaves(bbh_tree* t, uint32_t* leaf_ids, uint64_t* n_samples,
                            uint8_t* packed_centroids, void* linear_sums, int32_t ls_width);
 
 /* Gather selected leaves (by position in chain order) as BitFeature buffer rows
  * [linear_sum | n_samples] of `width` bytes -- the table BitBirch._bf_to_np /
  * multiround's round files hold (bitbirch.py:1292-1308, multiround.py:132-143).
- * positions: m int64 (host); out: m x (F+1) elements, host or device. */
+ * positions: m int64 (host), any order, repeats allowed; out: m x (F+1) elements, host or
+ * device.  A position outside [0, leaf count) is BBH_ERR_INVALID and nothing is written. */
 int bbh_tree_gather_buffers(bbh_tree* t, const int64_t* positions, int64_t m,
                             int32_t width, void* out);
 

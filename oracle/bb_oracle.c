@@ -640,6 +640,7 @@ void bbo_tree_reset(bbo_tree* t) {
     t->first_leaf = NULL;
     t->next_id = 0;
     t->num_fitted = 0;
+    memset(t->stats, 0, sizeof(t->stats)); /* the counters restart with the tree, as the engine's do */
 }
 
 void bbo_tree_destroy(bbo_tree* t) {
