@@ -2438,6 +2438,7 @@ struct bbh_tree {
     size_t sys_ring_bytes = 0;
     uint32_t sys_cap_nodes = 0;
     int sys_G_alloc = 0;
+    uint32_t sys_ids_before = 0;  // BitFeature ids in use before its launch (sys_take_over -> sys_after_launch)
     uint64_t syscount[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t sys_off_left = 0;  // elements the other kernels take after the systolic one refused the tree
     bool sys_pref = false;     // (default policy) this tree goes to the systolic kernel: the pipelined one asked for its multi-level
@@ -2445,6 +2446,46 @@ struct bbh_tree {
 };
 
 namespace {
+
+// the value of a switch that is on: set, not empty and not "0" (else null)
+static const char* env_value(const char* name) {
+    const char* v = getenv(name);
+    return (v != nullptr && v[0] != '\0' && std::strcmp(v, "0") != 0) ? v : nullptr;
+}
+
+// The switches that are read ONCE per process, at the first use (tree_env): diagnostics and experiments that a process sets
+// before it starts.  Not here, because tests flip them inside one process and so they are read on every call: BBHIP_TINY_POOLS,
+// BBHIP_GC, BBHIP_GC_MIN_MB, BBHIP_SYS, BBHIP_SLAB_KB (and BBHIP_ASSIGN, BBHIP_CACHE_MB in the other files).
+struct TreeEnv {
+    bool launch_log;         // BBHIP_LAUNCH_LOG (set, not empty, not "0"): one line per launch on stderr (tools/)
+    bool phases;             // BBHIP_PHASES: the phase-timer instances of the steady-state kernel / the complete engine; no pipeline
+    bool no_fixed_shape;     // BBHIP_NO_FIXED_SHAPE: no kernel compiled for bf 50 / 254 with 2048-bit rows
+    bool no_fast;            // BBHIP_NO_FAST: no steady-state kernel (and so no pipelined one)
+    bool no_pipe;            // BBHIP_NO_PIPE: no pipelined kernel
+    bool no_pipe_multi;      // BBHIP_NO_PIPE_MULTI: ... for several trees in one launch
+    int pipe_audit;          // BBHIP_PIPE_AUDIT: 0 off, 1 the pipelined kernel's run-end audit, 2 ("corrupt") with a planted difference
+    bool pipe_phases;        // BBHIP_PIPE_PHASES: the pipelined kernel's phase-timer instances
+    bool sys_phases;         // BBHIP_SYS_PHASES: the systolic kernel's
+    bool sys_debug;          // BBHIP_SYS_DEBUG: the systolic kernel's stale-control-word line and wait-state dump
+    bool no_singleton_path;  // BBHIP_NO_SINGLETON_PATH: uint8 buffers of one member are not packed into fingerprints
+    bool gc_log;             // BBHIP_GC_LOG: one line per compaction
+    int dense;               // BBHIP_DENSE: 0 / 1 forces one / two workgroups per CU in the complete engine (-1: unset)
+    char sys_mem;            // BBHIP_SYS_MEM, first letter: 'h'ost, 'p'lain, 'f'ine-grained (0: uncached device memory)
+    int sys_internal_wgs, sys_leaf_wgs;  // BBHIP_SYS_INTERNAL_WGS / _LEAF_WGS: owners per internal / leaf level (0: the plan's own)
+};
+static const TreeEnv& tree_env() {
+    static const TreeEnv env = [] {
+        auto set = [](const char* n) { return getenv(n) != nullptr; };
+        auto num = [](const char* n, int unset) { const char* v = getenv(n); return v ? atoi(v) : unset; };
+        const char* au = getenv("BBHIP_PIPE_AUDIT");
+        const char* sm = getenv("BBHIP_SYS_MEM");
+        return TreeEnv{env_value("BBHIP_LAUNCH_LOG") != nullptr, set("BBHIP_PHASES"), set("BBHIP_NO_FIXED_SHAPE"), set("BBHIP_NO_FAST"), set("BBHIP_NO_PIPE"),
+                       set("BBHIP_NO_PIPE_MULTI"), au == nullptr ? 0 : (std::strcmp(au, "corrupt") == 0 ? 2 : 1), set("BBHIP_PIPE_PHASES"), set("BBHIP_SYS_PHASES"),
+                       set("BBHIP_SYS_DEBUG"), set("BBHIP_NO_SINGLETON_PATH"), set("BBHIP_GC_LOG"), num("BBHIP_DENSE", -1), sm ? sm[0] : '\0',
+                       num("BBHIP_SYS_INTERNAL_WGS", 0), num("BBHIP_SYS_LEAF_WGS", 0)};
+    }();
+    return env;
+}
 
 // `used_elems`: the prefix of the old pool that holds live data (only that much is carried over)
 template <typename T>
@@ -2463,10 +2504,7 @@ int grow_pool(T*& p, size_t used_elems, size_t new_elems) {
 
 // BBHIP_TINY_POOLS=1 (tests): pools are pre-grown by next to nothing, so that the kernels run out of nodes / cluster-feature
 // slots in the middle of their runs and every STOP_* -> grow -> relaunch path is exercised
-static bool tiny_pools() {  // (read on every call: tests switch it on and off inside one process)
-    const char* v = getenv("BBHIP_TINY_POOLS");
-    return v != nullptr && v[0] != '\0' && std::strcmp(v, "0") != 0;
-}
+static bool tiny_pools() { return env_value("BBHIP_TINY_POOLS") != nullptr; }  // (read on every call: tests switch it on and off inside one process)
 // a pool that has to grow grows by at least half (a tree fed in 64 MiB slabs asked for a slightly larger pool with every
 // slab, i.e. copied all of it every time); `hint` is what the caller expects to need
 static uint32_t grow_target(uint32_t cap, uint32_t want, size_t elem_bytes = 0) {
@@ -2642,8 +2680,7 @@ int gc_nodes(bbh_tree* t, uint64_t extra, int seal) {
         h.ctr[C_ROOT] = new_root;
         h.ctr[C_FIRST_LEAF] = new_first;
         t->chain_valid = false;
-        static const bool gc_log = getenv("BBHIP_GC_LOG") != nullptr;
-        if (gc_log)
+        if (tree_env().gc_log)
             fprintf(stderr, "[bbhip gc] #%llu blocks %u -> %u (%.3f -> %.3f GB), nodes full %llu sealed %llu, new pool %.3f GB\n", (unsigned long long)t->gc_runs, used, total,
                     (double)used * (double)block_bytes(h) / 1e9, (double)total * (double)block_bytes(h) / 1e9, cnt[0], cnt[1], (double)want * (double)block_bytes(h) / 1e9);
         return BBH_OK;
@@ -2769,6 +2806,7 @@ int set_tol(bbh_tree* t, const double* tab, int64_t len) {
     return BBH_OK;
 }
 
+static int sys_allow_lds();  // (bb_tree_sys_host.inc)
 int configure(bbh_tree* t, int32_t bf, int32_t n_features) {
     TreeDev& h = t->h;
     h.bf = bf;
@@ -2813,10 +2851,7 @@ int configure(bbh_tree* t, int32_t bf, int32_t n_features) {
                 return bb::fail(BBH_ERR_NO_DEVICE, "device %d offers %d bytes of LDS per workgroup, the tree kernels need %u", t->device, cap,
                                 pipe_layout(254).total);
             }
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_sys<KS50>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KS50::o.total + sys_lds_bytes<KS50>())));
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_sys<KS254>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KS254::o.total + sys_lds_bytes<KS254>())));
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_sys<KS50, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KS50::o.total + sys_lds_bytes<KS50>())));
-            BB_HIP(hipFuncSetAttribute((const void*)k_tree_sys<KS254, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KS254::o.total + sys_lds_bytes<KS254>())));
+            BB_TRY(sys_allow_lds());
             attr_done_dev[di] = true;
         }
     }
@@ -2827,13 +2862,11 @@ int configure(bbh_tree* t, int32_t bf, int32_t n_features) {
 // of them fit in the CU's 160 KiB of LDS
 static bool dense_launch(size_t n_trees, size_t lds_bytes) {
     static int cus = -1;
-    static int mode = -1;  // BBHIP_DENSE=0/1 forces the choice (measurements)
+    const int mode = tree_env().dense;  // BBHIP_DENSE=0/1 forces the choice (measurements)
     if (cus < 0) {
         int dev = 0;
         hipDeviceProp_t p;
         cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 256;
-        const char* e = getenv("BBHIP_DENSE");
-        mode = e ? atoi(e) : -1;
     }
     if (mode >= 0) return mode != 0 && 2 * lds_bytes <= 160 * 1024;
     return n_trees > (size_t)cus && 2 * lds_bytes <= 160 * 1024;
@@ -2846,6 +2879,11 @@ static bool dense_launch(size_t n_trees, size_t lds_bytes) {
 //   appended buffer of several members - an eighth of the elements is more than any workload measured took (S-fake 3 %,
 //   S-ecfp 1 %, S-rdkit-like 10 %); nodes: one per bf / 2 elements (a node is half full after its split); tracking cluster
 //   features (uint32): two per node split.
+static uint64_t expected_node_blocks(const TreeDev& h, uint64_t n) { return (n / (uint64_t)std::max(1, h.bf / 2) + 64) * node_blocks((uint32_t)h.bf + 1); }
+static uint64_t expected_cf32_slots(const TreeDev& h, uint64_t n) { return n / (uint64_t)std::max(1, h.bf / 6) + 256; }
+// BBHIP_TINY_POOLS: what a pool is given instead - one insertion's worst case (a split of every level) and a little
+static uint64_t tiny_reserve(const TreeDev& h) { return 8 + 2 * (uint64_t)h.ctr[C_DEPTH]; }
+
 int pregrow(bbh_tree* t, int64_t n, int width) {
     TreeDev& h = t->h;
     const bool first = t->lazy_pools;  // the tree's pools come into being here: every pool at least at its minimum
@@ -2860,7 +2898,7 @@ int pregrow(bbh_tree* t, int64_t n, int width) {
     if (tiny_pools()) {
         BB_TRY(grow_cf(t, 0, clamp30((uint64_t)h.ctr[C_N8] + 8)));
         BB_TRY(grow_cf(t, 1, clamp30((uint64_t)h.ctr[C_N16] + 8)));
-        BB_TRY(grow_nodes(t, clamp30((uint64_t)h.ctr[C_NODES] + (8 + 2 * (uint64_t)h.ctr[C_DEPTH]) * node_blocks((uint32_t)h.bf + 1))));
+        BB_TRY(grow_nodes(t, clamp30((uint64_t)h.ctr[C_NODES] + tiny_reserve(h) * node_blocks((uint32_t)h.bf + 1))));
         BB_TRY(grow_cf(t, 2, clamp30((uint64_t)h.ctr[C_N32] + 16 + 2 * (uint64_t)h.ctr[C_DEPTH])));
         commit.ok = true;
         return BBH_OK;
@@ -2868,8 +2906,8 @@ int pregrow(bbh_tree* t, int64_t n, int width) {
     const uint64_t un = (uint64_t)std::max<int64_t>(n, 0);
     if (width <= 1 || first) BB_TRY(grow_cf(t, 0, clamp30((uint64_t)h.ctr[C_N8] + (width <= 1 ? un / 8 : 0) + 1024)));
     if (width == 2 || first) BB_TRY(grow_cf(t, 1, clamp30((uint64_t)h.ctr[C_N16] + (width == 2 ? un : 0) + 64)));
-    BB_TRY(grow_nodes(t, clamp30((uint64_t)h.ctr[C_NODES] + (un / (uint64_t)std::max(1, h.bf / 2) + 64) * node_blocks((uint32_t)h.bf + 1))));
-    BB_TRY(grow_cf(t, 2, clamp30((uint64_t)h.ctr[C_N32] + un / (uint64_t)std::max(1, h.bf / 6) + 256)));
+    BB_TRY(grow_nodes(t, clamp30((uint64_t)h.ctr[C_NODES] + expected_node_blocks(h, un))));
+    BB_TRY(grow_cf(t, 2, clamp30((uint64_t)h.ctr[C_N32] + expected_cf32_slots(h, un))));
     commit.ok = true;
     return BBH_OK;
 }
@@ -2896,196 +2934,159 @@ struct Job {
     int64_t old_left = 0;  // elements the steady-state kernel takes next (the pipelined one reported a shape it does not handle)
 };
 
-// ---- the level-systolic kernel's work area and launch plan (bb_tree_sys.inc) --------------------------------------------
-// the words workgroups talk through: uncached device memory (bb_tree_sys.inc, "Memory model")
-static bool sys_mem_host() {
-    static const bool h = [] { const char* m = getenv("BBHIP_SYS_MEM"); return m && m[0] == 'h'; }();
-    return h;
-}
-template <typename T>
-static hipError_t sys_alloc_uc(T** p, size_t bytes) {
-    if (sys_mem_host()) {  // (experiment: pinned host memory, coherent by construction, every access crosses the fabric)
-        hipError_t eh = hipHostMalloc((void**)p, bytes, hipHostMallocCoherent);
-        return eh;
+#include "bb_tree_sys_host.inc"
+
+// ---- which engine ran a launch, and what it is called where ---------------------------------------------------------------
+enum class Engine { Pipe, Fast, Complete, Sys };
+struct EngineLabels {
+    const char *log, *log_phases;  // the launch-log name (tools/fit_workloads.py, tools/merge_round_phases.py parse it); ... of the phase-timer instance
+    const char* prof;              // bb::prof_rename
+    int kcol;                      // column of bbh_tree::kcount (the systolic kernel counts with the pipelined one)
+};
+static const EngineLabels kEngineLabels[] = {{"pipe", "pipe", "tree_insert/pipe", 0}, {"fast", "fast+phases", "tree_insert/fast", 1},
+                                             {"complete", "complete", "tree_insert/complete", 2}, {"sys", "sys", "tree_insert/sys", 0}};  // (by Engine)
+
+// BBHIP_LAUNCH_LOG: one line per launch on stderr.  Called after the read-back and before the trees' own counters are
+// updated: the trees still hold the counters from before the launch, `harr` the ones from after it.
+static void print_launch_log(const char* name, const std::vector<Job>& jobs, const std::vector<size_t>& active, const std::vector<TreeDev>& harr,
+                             std::chrono::steady_clock::time_point t0) {
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    uint64_t d[6] = {0, 0, 0, 0, 0, 0};
+    long long done = 0;
+    for (size_t a = 0; a < active.size(); ++a) {
+        for (int z = 0; z < 6; ++z) d[z] += harr[a].stats[z] - jobs[active[a]].t->h.stats[z];
+        done += harr[a].processed;
     }
-    static const unsigned flags = [] {
-        const char* m = getenv("BBHIP_SYS_MEM");  // (experiments: "plain" = ordinary device memory, "fine" = fine-grained)
-        if (m && m[0] == 'p') return (unsigned)hipDeviceMallocDefault;
-        if (m && m[0] == 'f') return (unsigned)hipDeviceMallocFinegrained;
-        return (unsigned)hipDeviceMallocUncached;
-    }();
-    hipError_t e = hipExtMallocWithFlags((void**)p, bytes, flags);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        bb::dev_trim();
-        e = hipExtMallocWithFlags((void**)p, bytes, flags);
-    }
-    return e;
-}
-void sys_free(bbh_tree* t) {
-    void* uc[] = {t->sys.rings, t->sys.mail, t->sys.ctl};
-    for (void* q : uc)
-        if (q) (void)(sys_mem_host() ? hipHostFree(q) : hipFree(q));
-    void* ptrs[] = {t->sys.laste, t->sys.busy, t->sys.sent, t->sys.up, t->sys.acks};
-    for (void* q : ptrs)
-        if (q) bb::dev_free(q);
-    t->sys = SysDev{};
-    t->sys_ring_bytes = 0;
-    t->sys_cap_nodes = 0;
-    t->sys_G_alloc = 0;
+    const Job& j0 = jobs[active[0]];
+    fprintf(stderr, "[bbhip launch] %s trees=%zu %s crit=%d elems=%lld %.2f ms (%.2f us/elem) calls=%llu rows=%llu merges=%llu appends=%llu "
+            "leaf_splits=%llu node_splits=%llu stop=%d\n", name, active.size(), j0.bufs ? (j0.width == 1 ? "buf8" : j0.width == 2 ? "buf16" : "buf32+") : "packed",
+            j0.t->h.crit, done, ms, done ? 1e3 * ms / (double)done : 0.0, (unsigned long long)d[0], (unsigned long long)d[1], (unsigned long long)d[2],
+            (unsigned long long)d[3], (unsigned long long)d[4], (unsigned long long)d[5], harr[0].stop_reason);
 }
 
-// BBHIP_SYS: unset / "0" never (the default: the kernel is OPT-IN), "1" whenever the tree's shape allows it, "auto": where
-// the other kernels are weakest (see the selection in run_insert_multi).  Opt-in because its cross-workgroup hand-over is not
-// yet dependable on this hardware: the 1 M-row workloads it was built for are per-element identical to the oracle in every one
-// of ~100 runs, but the randomised suite's adversarial shapes at bf 254 (every node full, four levels, a split every few
-// elements) end in a detected inconsistency or - rarely - a silently different tree in 2-7 % of runs
-// (profiles/r06/sys_stability.txt).  Read on every call: tests switch it inside one process.
-static int sys_mode() {
-    const char* v = getenv("BBHIP_SYS");
-    if (v == nullptr || v[0] == '\0' || std::strcmp(v, "0") == 0) return 0;
-    if (std::strcmp(v, "auto") == 0) return 2;
-    return 1;
+// BBHIP_PIPE_PHASES (bbh_tree_stats): the pipelined kernel's phase timers
+static void print_pipe_phases(const bbh_tree* t) {
+    static const char* nm[16] = {"router:setup", "router:wait", "router:compare", "router:commit", "router:drain", "leaf:wait", "leaf:fill",
+                                 "leaf:compare", "leaf:cf+dot", "leaf:decide+apply", "all:flush", "all:cold", "#runs", "#router-stale", "#leaf-pre-hits", "#leaf-stale"};
+    const double n = (double)(t->h.stats[2] + t->h.stats[3]);
+    fprintf(stderr, "[bbhip pipe phases, per insert]");
+    for (int i = 0; i < 16; ++i) fprintf(stderr, " %s=%.*f", nm[i], i < 12 ? 0 : 4, n > 0 ? (double)t->h.phase[i] / n : 0.0);
+    static const char* kd[3] = {"pre-compared, best row folded", "own", "pre-compared, every row checked"};
+    fprintf(stderr, "\n[bbhip pipe leaf compares]");
+    for (int i = 0; i < 3; ++i)
+        fprintf(stderr, " %s: %.3f/insert x %.0f cycles", kd[i], n > 0 ? (double)t->h.sphase[2 * i + 1] / n : 0.0,
+                t->h.sphase[2 * i + 1] ? (double)t->h.sphase[2 * i] / (double)t->h.sphase[2 * i + 1] : 0.0);
+    fprintf(stderr, "\n");
+    fprintf(stderr, "[bbhip pipe router waits, per insert] ring entry %.0f, row + pre-compare of wave 2 %.0f, pending jobs of a nearly full leaf %.0f, "
+            "decision on a full leaf %.0f\n", n > 0 ? (double)t->h.rprof[0] / n : 0.0, n > 0 ? (double)t->h.rprof[1] / n : 0.0,
+            n > 0 ? (double)t->h.rprof[2] / n : 0.0, n > 0 ? (double)t->h.rprof[3] / n : 0.0);
+    if (t->h.splitprof[8]) {
+        const double ns = (double)t->h.splitprof[8];
+        fprintf(stderr, "[bbhip pipe leaf splits] %.4f/insert x %.0f cycles:", n > 0 ? ns / n : 0.0, (double)t->h.splitprof[9] / ns);
+        for (int i = 0; i < 8; ++i) fprintf(stderr, " s%d=%.0f", i, (double)t->h.splitprof[i] / ns);
+        fprintf(stderr, "\n");
+    }
+    if (t->pipe_ml)
+        fprintf(stderr, "[bbhip pipe multi-level router] upper-slot fills %.3f/insert x %.0f cycles; tracking levels committed %.3f/insert, "
+                "cluster-feature cache misses %.3f/insert; router waiting for a level's update by a helper wave %.0f cycles/insert, for "
+                "all of them and their stores (before a fill) %.0f; of a fill: loads %.0f cycles, slot + corrections %.0f\n", n > 0 ? (double)t->h.sphase[7] / n : 0.0,
+                t->h.sphase[7] ? (double)t->h.sphase[6] / (double)t->h.sphase[7] : 0.0, n > 0 ? (double)t->h.mlprof[1] / n : 0.0,
+                n > 0 ? (double)t->h.mlprof[0] / n : 0.0, n > 0 ? (double)t->h.mlprof[2] / n : 0.0, n > 0 ? (double)t->h.mlprof[3] / n : 0.0,
+                t->h.sphase[7] ? (double)t->h.mlprof[4] / (double)t->h.sphase[7] : 0.0, t->h.sphase[7] ? (double)t->h.mlprof[5] / (double)t->h.sphase[7] : 0.0);
 }
 
-// Are the root's centroids informative (some row's popcount non-zero)?  Trees over sparse / weakly clustered rows keep
-// all-zero centroids in their upper levels (every similarity 0, np.argmax -> row 0): one exact level, the shape the pipelined
-// kernel was built for (S-fake: 460 k/s there, 274 k/s here).  Trees over real-fingerprint-like rows compare at every level:
-// that is what the systolic kernel is for (zipf / hier: 122-131 k/s there, 357-379 k/s here).  Two small blocking copies, made
-// only when the pipelined kernel has just handed the tree over.
-static bool sys_root_informative(bbh_tree* t) {
+// BBHIP_PHASES (bbh_tree_stats): the phase timers of the steady-state kernel and the complete engine
+static void print_phases(const bbh_tree* t) {
+    fprintf(stderr, "[bbhip phases, cycles/insert]");
+    const double n = (double)(t->h.stats[2] + t->h.stats[3]);
+    for (int i = 0; i < 8; ++i) fprintf(stderr, " p%d=%.0f", i, n > 0 ? (double)t->h.phase[i] / n : 0.0);
+    static const char* cls[3] = {"fill/miss", "tag-only", "compare"};  // (k_tree_fast; k_tree_insert: miss, zero-skip, mirror-hit)
+    fprintf(stderr, "\n[bbhip p0 detail] loop-top barrier+checks=%.0f wait-for-prefetched-row=%.0f", n > 0 ? (double)t->h.phase[14] / n : 0.0,
+            n > 0 ? (double)t->h.phase[15] / n : 0.0);
+    for (int i = 0; i < 3; ++i)
+        fprintf(stderr, "\n[bbhip descent] %-10s levels/insert=%.3f cycles/level=%.0f", cls[i],
+                n > 0 ? (double)t->h.phase[11 + i] / n : 0.0,
+                t->h.phase[11 + i] ? (double)t->h.phase[8 + i] / (double)t->h.phase[11 + i] : 0.0);
+    fprintf(stderr, "\n[bbhip split phases, cycles/split]");
+    const double ns = (double)t->h.stats[4];
+    for (int i = 0; i < 8; ++i) fprintf(stderr, " s%d=%.0f", i, ns > 0 ? (double)t->h.sphase[i] / ns : 0.0);
+    fprintf(stderr, "\n");
+}
+
+// ---- which kernel instance the active trees can share ------------------------------------------------------------------------
+// trees of the benchmark / default shape run the kernels compiled for that shape: the branching factor all of them have (with
+// 2048-bit rows), 50 or 254, or 0
+static int fixed_bf(const std::vector<Job>& jobs, const std::vector<size_t>& active) {
+    bool all50 = !tree_env().no_fixed_shape, all254 = all50;
+    for (size_t a = 0; a < active.size() && (all50 || all254); ++a) {
+        const TreeDev& q = jobs[active[a]].t->h;
+        all50 = all50 && q.bf == 50 && q.F == 2048;
+        all254 = all254 && q.bf == 254 && q.F == 2048;
+    }
+    return all50 ? 50 : (all254 ? 254 : 0);
+}
+
+// the steady-state kernel: 2048-bit rows, bf 50 / 254, criteria without extra reductions, all trees with packed rows or all
+// with buffers.  Null: the complete engine.
+static const FastKernel* choose_fast(const std::vector<Job>& jobs, const std::vector<size_t>& active, int bf) {
+    if (tree_env().no_fast || bf == 0) return nullptr;
+    bool packed = true, buffers = true;
+    int crit = jobs[active[0]].t->h.crit;  // the criterion all trees share, or -1
+    for (size_t a = 0; a < active.size(); ++a) {
+        const Job& fj = jobs[active[a]];
+        const int c = fj.t->h.crit;
+        if (c != crit) crit = -1;
+        if (c != BBH_CRIT_DIAMETER && c != BBH_CRIT_TOL_DIAMETER && c != BBH_CRIT_TOL_LEGACY && c != BBH_CRIT_NEVER) return nullptr;
+        packed = packed && fj.bufs == nullptr;
+        buffers = buffers && fj.bufs != nullptr;
+        // packed rows are read with 16-byte loads straight into registers
+        if (fj.bufs == nullptr && ((((uintptr_t)fj.rows) | (uintptr_t)fj.row_stride) & 15) != 0) return nullptr;
+    }
+    if (!packed && !buffers) return nullptr;
+    for (const FastKernel& c : kFastKernels)
+        if (c.bf == bf && c.buffers == buffers && (c.crit == -1 || c.crit == crit)) return &c;
+    return nullptr;
+}
+
+// the pipelined kernel, for trees that may enter it (see `pipe_possible` in run_insert_multi): every tree must be ready for it
+// (none on a stretch of the steady-state kernel), and they share one instance.  Null: the steady-state kernel.
+static const PipeKernel* choose_pipe(const std::vector<Job>& jobs, const std::vector<size_t>& active, int bf) {
+    int want_ml = 0, crit = jobs[active[0]].t->h.crit;
+    for (size_t a = 0; a < active.size(); ++a) {
+        const Job& pj = jobs[active[a]];
+        if (pj.old_left != 0 || pj.t->h.n_elems >= (1ll << 31)) return nullptr;
+        if (pj.t->h.crit != crit) crit = -1;
+        want_ml |= pj.t->pipe_ml ? 1 : 0;  // (the multi-level instance also runs trees of one exact level)
+    }
+    for (const PipeKernel& c : kPipeKernels)
+        if (c.bf == bf && c.crit == crit && c.ml == want_ml) return &c;
+    return nullptr;
+}
+
+// ---- growing the pool a kernel ran out of ---------------------------------------------------------------------------------
+// A pool that ran out (STOP_NODES / STOP_CF*) is grown to half as much again, or to what the `left` elements are expected to
+// need if that is more.  The expectations are pregrow's, with two differences that are kept on purpose: uint8 slots are
+// expected here whatever the elements' width (pregrow: only for width <= 1), and uint16 slots at left / 64 for widths other
+// than 2 (pregrow: none).
+int grow_after_stop(bbh_tree* t, const Job& j, const TreeDev& back, int64_t left) {
     const TreeDev& h = t->h;
-    const uint32_t root = h.ctr[C_ROOT];
-    NodeHdr hd{};
-    if (hipMemcpy(&hd, h.node_hdr + root, sizeof(hd), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return false; }
-    const uint32_t len = std::min<uint32_t>(hd.len, (uint32_t)h.bf + 1);
-    if (len == 0 || (hd.leaf & HW_LEAF)) return false;
-    std::vector<uint32_t> cards(len);
-    if (hipMemcpy(cards.data(), h.node_card + (size_t)root * NG, (size_t)len * 4, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return false; }
-    for (uint32_t cd : cards)
-        if (cd != 0) return true;
-    return false;
-}
-
-// workgroups per tree level: level 0 is workgroup 0 (the root), the last level the leaf owners
-static void sys_plan(const TreeDev& h, SysDev& S) {
-    const int levels = (int)h.ctr[C_DEPTH];  // (1: the root is a leaf)
-    S.levels = levels;
-    int first = 0;
-    static const int env_int = [] { const char* v = getenv("BBHIP_SYS_INTERNAL_WGS"); return v ? atoi(v) : 0; }();
-    static const int env_leaf = [] { const char* v = getenv("BBHIP_SYS_LEAF_WGS"); return v ? atoi(v) : 0; }();
-    for (int l = 0; l < levels && l < SYS_MAXLVL; ++l) {
-        int cnt;
-        if (l == 0) cnt = 1;
-        else if (l == levels - 1) cnt = env_leaf > 0 ? env_leaf : 64;
-        else cnt = env_int > 0 ? env_int : (h.bf >= 128 ? 64 : 16);  // (bf 254: one mirrored node per owner - as many owners as a level has nodes)
-        cnt = std::min(cnt, SYS_MAXPROD);
-        while (cnt & (cnt - 1)) cnt &= cnt - 1;  // a power of two (sys_owner_idx)
-        S.lvl_first[l] = first;
-        S.lvl_count[l] = cnt;
-        first += cnt;
-    }
-    S.G = first;
-    // every workgroup has to be RESIDENT (one per CU: the kernel takes most of a CU's LDS) - a workgroup that waits for a CU while
-    // the others wait for its answers is a deadlock (found by the randomised suite: five levels at bf 254 came to 257 workgroups)
-    while (S.G > 224) {
-        first = 0;
-        for (int l = 0; l < levels && l < SYS_MAXLVL; ++l) {
-            if (l > 0 && l < levels - 1 && S.lvl_count[l] > 8) S.lvl_count[l] /= 2;
-            S.lvl_first[l] = first;
-            first += S.lvl_count[l];
-        }
-        if (first == S.G) break;
-        S.G = first;
-    }
-    S.qmax = 384;  // (< SYS_R: no ring can overflow)
-}
-
-// (re)allocate what the plan and the node pool's size need; zero the rings and control words, initialise the mailboxes
-static int sys_prepare(bbh_tree* t, hipStream_t s) {
-    TreeDev& h = t->h;
-    SysDev& S = t->sys;
-    sys_plan(h, S);
-    {
-        // the kernel admits an element only while the pools hold the worst case of everything in flight (every element splits
-        // every level and the root): make sure a launch starts with that reserve and room to work in
-        const uint64_t q = (uint64_t)S.qmax + 64, depth = h.ctr[C_DEPTH], nblk = node_blocks((uint32_t)h.bf + 1);
-        const uint64_t room = tiny_pools() ? 16 : 4096;  // (elements' worth of room beyond the reserve)
-        BB_TRY(grow_nodes(t, clamp30((uint64_t)h.ctr[C_NODES] + (q * (depth + 2) + room / 8 + 8) * nblk)));
-        BB_TRY(grow_cf(t, 0, clamp30((uint64_t)h.ctr[C_N8] + q + room)));
-        BB_TRY(grow_cf(t, 1, clamp30((uint64_t)h.ctr[C_N16] + q + 64)));
-        BB_TRY(grow_cf(t, 2, clamp30((uint64_t)h.ctr[C_N32] + q * 2 * (depth + 2) + room / 4 + 16)));
-    }
-    const size_t ring_bytes = (size_t)S.G * SYS_MAXPROD * (size_t)SYS_R * 16;
-    {
-        static std::atomic<uint32_t> g_sys_launch{0};  // (process-wide: a new tree may inherit another tree's ring memory)
-        S.launch_id = (g_sys_launch.fetch_add(1u) + 1u) & 0x7FFFFFFFu;
-        if (S.launch_id == 0) S.launch_id = (g_sys_launch.fetch_add(1u) + 1u) & 0x7FFFFFFFu;
-    }
-    if (ring_bytes > t->sys_ring_bytes || S.G > t->sys_G_alloc) {
-        if (S.rings) (void)(sys_mem_host() ? hipHostFree(S.rings) : hipFree(S.rings));
-        if (S.busy) bb::dev_free(S.busy);
-        S.rings = nullptr; S.busy = nullptr;
-        BB_HIP(sys_alloc_uc(&S.rings, ring_bytes));
-        BB_HIP(bb::dev_alloc(&S.busy, (size_t)S.G * (15 * 8 + 3 * SYS_MAXPROD * 4) + 64));
-        t->sys_ring_bytes = ring_bytes;
-        t->sys_G_alloc = S.G;
-    }
-    if (!S.ctl) BB_HIP(sys_alloc_uc(&S.ctl, SC_COUNT * 4));
-    if (h.cap_nodes > t->sys_cap_nodes || !S.mail) {
-        if (S.mail) (void)(sys_mem_host() ? hipHostFree(S.mail) : hipFree(S.mail));
-        if (S.sent) bb::dev_free(S.sent);
-        if (S.up) bb::dev_free(S.up);
-        if (S.laste) bb::dev_free(S.laste);
-        if (S.acks) bb::dev_free(S.acks);
-        S.mail = nullptr; S.sent = nullptr; S.up = nullptr; S.laste = nullptr; S.acks = nullptr;
-        BB_HIP(bb::dev_alloc(&S.laste, (size_t)h.cap_nodes * 4 + 64));
-        BB_HIP(bb::dev_alloc(&S.acks, (size_t)h.cap_nodes * 4 + 64));
-        BB_HIP(bb::dev_alloc(&S.sent, (size_t)h.cap_nodes * 4 + 64));
-        BB_HIP(bb::dev_alloc(&S.up, (size_t)h.cap_nodes * 8 + 64));
-        BB_HIP(sys_alloc_uc(&S.mail, (size_t)h.cap_nodes * 8 + 64));
-        t->sys_cap_nodes = h.cap_nodes;
-    }
-    BB_HIP(hipMemsetAsync(S.rings, 0, ring_bytes, s));
-    BB_HIP(hipMemsetAsync(S.ctl, 0, SC_COUNT * 4, s));
-    BB_HIP(hipMemsetAsync(S.busy, 0, (size_t)S.G * (15 * 8 + 3 * SYS_MAXPROD * 4), s));
-    const uint32_t used = std::min(h.cap_nodes, h.ctr[C_NODES]);
-    hipLaunchKernelGGL(k_sys_init, dim3((used + 255) / 256), dim3(256), 0, s, (const NodeHdr*)h.node_hdr, used, S.mail, S.sent, S.up, S.laste, S.acks);
-    BB_HIP(hipGetLastError());
-    return BBH_OK;
-}
-
-// ids handed out by a launch of the systolic kernel, renumbered into the sequential engines' order (bb_tree_sys.inc)
-static int sys_renumber(bbh_tree* t, uint32_t* out_leaf, uint32_t n, uint32_t base, uint32_t nnew, hipStream_t s) {
-    if (out_leaf == nullptr || n == 0 || nnew == 0) return BBH_OK;
-    uint32_t *creator = nullptr, *flag = nullptr, *rank = nullptr, *map = nullptr;
-    void* tmp = nullptr;
-    auto body = [&]() -> int {
-        BB_HIP(bb::dev_alloc(&creator, (size_t)nnew * 4 + 64));
-        BB_HIP(bb::dev_alloc(&flag, (size_t)n * 4 + 64));
-        BB_HIP(bb::dev_alloc(&rank, (size_t)n * 4 + 64));
-        BB_HIP(bb::dev_alloc(&map, (size_t)nnew * 4 + 64));
-        BB_HIP(hipMemsetAsync(creator, 0xFF, (size_t)nnew * 4, s));
-        const dim3 ge((n + 255) / 256), gi((nnew + 255) / 256), blk(256);
-        hipLaunchKernelGGL(k_sys_creator, ge, blk, 0, s, (const uint32_t*)out_leaf, n, base, creator);
-        hipLaunchKernelGGL(k_sys_flag, ge, blk, 0, s, (const uint32_t*)out_leaf, n, base, (const uint32_t*)creator, flag);
-        size_t tmp_bytes = 0;
-        BB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, flag, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
-        BB_HIP(bb::dev_alloc(&tmp, tmp_bytes + 16));
-        BB_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, flag, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
-        hipLaunchKernelGGL(k_sys_map, gi, blk, 0, s, (const uint32_t*)creator, (const uint32_t*)rank, nnew, base, map);
-        hipLaunchKernelGGL(k_sys_apply_out, ge, blk, 0, s, out_leaf, n, base, nnew, (const uint32_t*)map);
-        const uint32_t used = std::min(t->h.cap_nodes, t->h.ctr[C_NODES]);
-        hipLaunchKernelGGL(k_sys_apply_rows, dim3((used + 3) / 4), blk, 0, s, (const NodeHdr*)t->h.node_hdr, t->h.node_rm, used, base, nnew, (const uint32_t*)map);
-        BB_HIP(hipGetLastError());
-        BB_HIP(hipStreamSynchronize(s));
-        return BBH_OK;
+    const bool tiny = tiny_pools();
+    const uint64_t n = (uint64_t)std::max<int64_t>(left, 0);
+    auto more = [&](uint32_t used, uint32_t cap, uint64_t expect) -> uint32_t {
+        if (tiny) return clamp30((uint64_t)cap + tiny_reserve(h));  // (one insertion's worst case fits)
+        return clamp30(std::max<uint64_t>((uint64_t)cap + 1, (uint64_t)used + expect));  // (grow_cf takes the larger of this and its geometric step)
     };
-    const int rc = body();
-    void* ptrs[] = {creator, flag, rank, map, tmp};
-    for (void* q : ptrs)
-        if (q) bb::dev_free(q);
-    return rc;
+    switch (back.stop_reason) {
+        case STOP_NODES: {
+            // (blocks; a pool that is compacted on the way - grow_nodes - takes `room` as the room asked for)
+            const uint64_t room = tiny ? tiny_reserve(h) * node_blocks((uint32_t)h.bf + 1) : expected_node_blocks(h, n);
+            return grow_nodes(t, clamp30(std::max<uint64_t>(tiny ? 0 : (uint64_t)h.cap_nodes + h.cap_nodes / 2, (uint64_t)h.ctr[C_NODES] + room)), room);
+        }
+        case STOP_CF8: return grow_cf(t, 0, more(h.ctr[C_N8], h.cap8, n / 8 + 1024));
+        case STOP_CF16: return grow_cf(t, 1, more(h.ctr[C_N16], h.cap16, (j.width == 2 ? n : n / 64) + 64));
+        case STOP_CF32: return grow_cf(t, 2, more(h.ctr[C_N32], h.cap32, expected_cf32_slots(h, n)));
+        default: return BBH_OK;
+    }
 }
 
 // Run the insertion kernel over all jobs, ONE WORKGROUP PER TREE in a single launch (independent
@@ -3093,6 +3094,7 @@ static int sys_renumber(bbh_tree* t, uint32_t* out_leaf, uint32_t n, uint32_t ba
 // ones after growing whatever pool made them stop.
 int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
     if (jobs.empty()) return BBH_OK;
+    const TreeEnv& env = tree_env();
     TreeDev* darr = nullptr;
     const bool single = jobs.size() == 1;
     if (!single) BB_HIP(bb::dev_alloc(&darr, jobs.size() * sizeof(TreeDev)));
@@ -3115,7 +3117,7 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
     size_t multi_left_midway = 0;  // trees that left a shared launch midway for an unsupported shape, over the whole call
     long long multi_chunk = 1ll << 15;  // elements per tree and shared launch: doubles (to 2^18) with every launch no tree left midway
     while (rc == BBH_OK) {
-        long long multi_requested = 0;
+        // ---- 1. the descriptors of the trees that have elements left
         active.clear();
         for (size_t i = 0; i < jobs.size(); ++i)
             if (jobs[i].done < jobs[i].n) active.push_back(i);
@@ -3132,194 +3134,122 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
             harr[a] = h;
         }
         TreeDev* dptr = single ? jobs[0].t->d : darr;
-        size_t prof_tok = (size_t)-1;
-        uint32_t sys_ids_before = 0;  // (the systolic kernel: BitFeature ids in use before its launch)
-        static const bool launch_log = [] {  // one line per launch on stderr (tools/); unset, empty or "0": off
-            const char* v = getenv("BBHIP_LAUNCH_LOG");
-            return v != nullptr && v[0] != '\0' && std::strcmp(v, "0") != 0;
-        }();
         const auto log_t0 = std::chrono::steady_clock::now();
-        const char* log_kernel = "complete";
-        uint64_t log_before[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (launch_log)
-            for (size_t a = 0; a < active.size(); ++a)
-                for (int z = 0; z < 8; ++z) log_before[z] += jobs[active[a]].t->h.stats[z];
         hipError_t e = hipMemcpyAsync(dptr, harr.data(), active.size() * sizeof(TreeDev), hipMemcpyHostToDevice, s);
         if (e != hipSuccess) { rc = bb::fail(BBH_ERR_HIP, "H2D: %s", hipGetErrorString(e)); break; }
+        size_t prof_tok = (size_t)-1;
+        Engine engine = Engine::Complete;
+        bool fast_phases = false;
+        long long multi_requested = 0;
         {
-            bb::ProfScope ps("tree_insert", s);
+            bb::ProfScope ps("tree_insert", s);  // (ends with the launch)
             prof_tok = ps.tok;
-            static const bool prof_phases = getenv("BBHIP_PHASES") != nullptr;
-            // trees of the benchmark / default shape run the kernel compiled for that shape
-            static const bool no_fix = getenv("BBHIP_NO_FIXED_SHAPE") != nullptr;
-            bool all50 = !no_fix, all254 = !no_fix;
-            for (size_t a = 0; a < active.size() && (all50 || all254); ++a) {
-                const TreeDev& q = jobs[active[a]].t->h;
-                all50 = all50 && q.bf == 50 && q.F == 2048;
-                all254 = all254 && q.bf == 254 && q.F == 2048;
-            }
-            // the steady-state kernel: 2048-bit rows, bf 50 / 254, criteria without extra reductions
-            static const bool no_fast = getenv("BBHIP_NO_FAST") != nullptr;
-            bool fast_ok = !no_fast && (all50 || all254);
-            bool f_packed = true, f_buffers = true;
-            int f_crit = active.empty() ? -1 : jobs[active[0]].t->h.crit;  // the criterion all trees share, or -1
-            for (size_t a = 0; a < active.size() && fast_ok; ++a) {
-                const Job& fj = jobs[active[a]];
-                const int c = fj.t->h.crit;
-                if (c != f_crit) f_crit = -1;
-                fast_ok = c == BBH_CRIT_DIAMETER || c == BBH_CRIT_TOL_DIAMETER || c == BBH_CRIT_TOL_LEGACY || c == BBH_CRIT_NEVER;
-                f_packed = f_packed && fj.bufs == nullptr;
-                f_buffers = f_buffers && fj.bufs != nullptr;
-                // packed rows are read with 16-byte loads straight into registers
-                if (fj.bufs == nullptr && ((((uintptr_t)fj.rows) | (uintptr_t)fj.row_stride) & 15) != 0) fast_ok = false;
-            }
-            fast_ok = fast_ok && (f_packed || f_buffers);
-            const FastKernel* fk = nullptr;
-            if (fast_ok)
-                for (const FastKernel& c : kFastKernels)
-                    if (fk == nullptr && c.bf == (all50 ? 50 : 254) && c.buffers == f_buffers && (c.crit == -1 || c.crit == f_crit)) fk = &c;
-            const dim3 grid((unsigned)active.size()), block(TB);
+            bool recopy = false;  // a descriptor changed after the upload
+
+            // ---- 2. the steady-state entry and the pipelined entry the trees can share
+            const int bf = fixed_bf(jobs, active);
+            const FastKernel* fk = choose_fast(jobs, active, bf);
             // The pipelined kernel: packed rows, the criteria of the standard pipelines.  Several trees (multiround shards,
             // one workgroup each): all of them must be ready for it - a tree that is on a stretch of the steady-state
             // kernel (old_left) takes the whole launch there, the others come along for the length of that stretch - and
             // a launch inserts at most `multi_chunk` elements per tree: a tree that stops early (a shape the pipeline
             // hands over, a pool that ran out) waits for the others' workgroups, and no longer than that.
-            static const bool no_pipe = getenv("BBHIP_NO_PIPE") != nullptr;
-            static const bool no_pipe_multi = getenv("BBHIP_NO_PIPE_MULTI") != nullptr;
-            const long long PIPE_MULTI_CHUNK = multi_chunk;
-            const PipeKernel* pk = nullptr;
-            const bool pipe_possible = fk != nullptr && !no_pipe && !prof_phases && f_packed && (single || (all254 && !no_pipe_multi && multi_pipe_ok));
-            bool recopy = false;
-            if (pipe_possible) {
-                bool all_ready = true;
-                int want_ml = 0;
-                int64_t max_old = 0;
+            const bool pipe_possible = fk != nullptr && !fk->buffers && !env.no_pipe && !env.phases && (single || (bf == 254 && !env.no_pipe_multi && multi_pipe_ok));
+            const PipeKernel* pk = pipe_possible ? choose_pipe(jobs, active, bf) : nullptr;
+            if (pk != nullptr && !single) {
                 for (size_t a = 0; a < active.size(); ++a) {
-                    const Job& pj = jobs[active[a]];
-                    all_ready = all_ready && pj.old_left == 0 && harr[a].n_elems < (1ll << 31);
-                    max_old = std::max(max_old, pj.old_left);
-                    want_ml |= pj.t->pipe_ml ? 1 : 0;  // (the multi-level instance also runs trees of one exact level)
+                    if (harr[a].n_elems > multi_chunk) { harr[a].n_elems = multi_chunk; recopy = true; }
+                    multi_requested += harr[a].n_elems;
                 }
-                if (all_ready) {
-                    for (const PipeKernel& c : kPipeKernels)
-                        if (pk == nullptr && c.bf == (all50 ? 50 : 254) && c.crit == f_crit && c.ml == want_ml) pk = &c;
-                    if (pk != nullptr && !single)
-                        for (size_t a = 0; a < active.size(); ++a) {
-                            if (harr[a].n_elems > PIPE_MULTI_CHUNK) { harr[a].n_elems = PIPE_MULTI_CHUNK; recopy = true; }
-                            multi_requested += harr[a].n_elems;
-                        }
-                } else if (!single && max_old > 0) {
-                    for (size_t a = 0; a < active.size(); ++a)
-                        if (jobs[active[a]].old_left == 0 && harr[a].n_elems > max_old) { harr[a].n_elems = max_old; recopy = true; }
-                }
-            }
-            // The level-systolic kernel (bb_tree_sys.inc): ONE tree over many workgroups.  BBHIP_SYS=1: whenever the shape allows;
-            // default: where the pipelined kernel has nothing to offer - it asked for its multi-level instance (informative levels
-            // above the leaf-parents at bf 50) or refused the shape (bf 254) and the steady-state kernel would take the stretch.
-            int64_t sys_n = 0;
-            static const bool pipe_diag = getenv("BBHIP_PIPE_AUDIT") != nullptr || getenv("BBHIP_PIPE_PHASES") != nullptr;  // (diagnostics of the pipelined kernel: keep it in charge)
-            if (!pipe_diag && single && fk != nullptr && f_packed && !prof_phases && sys_mode() != 0) {
-                Job& sj = jobs[active[0]];
-                bbh_tree* st = sj.t;
-                const int levels = (int)st->h.ctr[C_DEPTH];
-                const bool shape_ok = levels >= 2 && levels <= SYS_MAXLVL && st->gc_runs == 0 && harr[0].n_elems < (1ll << 31) && st->sys_off_left == 0;
-                if (shape_ok) {
-                    if (sys_mode() == 1) {
-                        sys_n = harr[0].n_elems;
-                    } else {
-                        if (!st->sys_pref && ((all254 && sj.old_left > 0) || (all50 && st->pipe_ml)) && sys_root_informative(st)) st->sys_pref = true;
-                        if (st->sys_pref) {
-                            sj.old_left = 0;  // (the stretch the steady-state kernel was to take is this kernel's, and so is the rest of the call)
-                            sys_n = sj.n - sj.done;
-                        }
-                    }
-                }
-                if (sys_n > 0) {
-                    pk = nullptr;
-                    sys_ids_before = st->h.ctr[C_IDS];
-                    rc = sys_prepare(st, s);
-                    if (rc != BBH_OK) break;
-                    harr[0] = st->h;  // (the pools may have grown)
-                    harr[0].n_elems = sys_n;
-                    recopy = true;
-                }
-            }
-            if (!pipe_possible && !single) {
+            } else if (pipe_possible && !single) {
+                int64_t max_old = 0;
+                for (size_t a = 0; a < active.size(); ++a) max_old = std::max(max_old, jobs[active[a]].old_left);
+                for (size_t a = 0; a < active.size() && max_old > 0; ++a)
+                    if (jobs[active[a]].old_left == 0 && harr[a].n_elems > max_old) { harr[a].n_elems = max_old; recopy = true; }
+            } else if (!single) {
                 // (the attempt is over: nobody comes back to the pipeline, the stretches are the rest of the input)
                 for (size_t a = 0; a < active.size(); ++a) {
                     Job& oj = jobs[active[a]];
                     if (oj.old_left > 0) { oj.old_left = 0; harr[a].n_elems = oj.n - oj.done; recopy = true; }
                 }
             }
-            if (pk != nullptr) {
-                // tier promotions of elements in flight take cf16 / cf32 slots without asking: keep a reserve
-                for (size_t a = 0; a < active.size() && rc == BBH_OK; ++a) {
-                    bbh_tree* ta = jobs[active[a]].t;
-                    bool grown = false;
-                    if (ta->h.cap16 - std::min(ta->h.cap16, ta->h.ctr[C_N16]) < (uint32_t)PROMO_RESERVE) {
-                        rc = grow_cf(ta, 1, clamp30((uint64_t)ta->h.ctr[C_N16] + 2 * PROMO_RESERVE));
-                        grown = true;
-                    }
-                    if (rc == BBH_OK && ta->h.cap32 - std::min(ta->h.cap32, ta->h.ctr[C_N32]) < (uint32_t)PROMO_RESERVE) {
-                        rc = grow_cf(ta, 2, clamp30((uint64_t)ta->h.ctr[C_N32] + 2 * PROMO_RESERVE));
-                        grown = true;
-                    }
-                    if (grown) {
-                        harr[a].cf16 = ta->h.cf16; harr[a].cf32 = ta->h.cf32; harr[a].cap16 = ta->h.cap16; harr[a].cap32 = ta->h.cap32;
-                        recopy = true;
-                    }
-                }
+
+            // ---- 3. the level-systolic kernel takes a single tree over where it is asked to (bb_tree_sys_host.inc)
+            int64_t sys_n = 0;
+            if (single && fk != nullptr) {
+                rc = sys_take_over(jobs[active[0]], *fk, s, &sys_n);
                 if (rc != BBH_OK) break;
             }
+            if (sys_n > 0) {
+                pk = nullptr;
+                harr[0] = jobs[active[0]].t->h;  // (the pools may have grown)
+                harr[0].n_elems = sys_n;
+                recopy = true;
+            }
+
+            // ---- 4. the pipelined kernel: tier promotions of elements in flight take cf16 / cf32 slots without asking: keep a reserve
+            for (size_t a = 0; pk != nullptr && a < active.size() && rc == BBH_OK; ++a) {
+                bbh_tree* ta = jobs[active[a]].t;
+                bool grown = false;
+                if (ta->h.cap16 - std::min(ta->h.cap16, ta->h.ctr[C_N16]) < (uint32_t)PROMO_RESERVE) {
+                    rc = grow_cf(ta, 1, clamp30((uint64_t)ta->h.ctr[C_N16] + 2 * PROMO_RESERVE));
+                    grown = true;
+                }
+                if (rc == BBH_OK && ta->h.cap32 - std::min(ta->h.cap32, ta->h.ctr[C_N32]) < (uint32_t)PROMO_RESERVE) {
+                    rc = grow_cf(ta, 2, clamp30((uint64_t)ta->h.ctr[C_N32] + 2 * PROMO_RESERVE));
+                    grown = true;
+                }
+                if (grown) {
+                    harr[a].cf16 = ta->h.cf16; harr[a].cf32 = ta->h.cf32; harr[a].cap16 = ta->h.cap16; harr[a].cap32 = ta->h.cap32;
+                    recopy = true;
+                }
+            }
+            if (rc != BBH_OK) break;
+            if (pk != nullptr && env.pipe_audit != 0) {
+                for (size_t a = 0; a < active.size(); ++a) harr[a].audit = env.pipe_audit;
+                recopy = true;
+            }
+
+            // ---- 5. one more upload if a descriptor changed
             if (recopy) {
                 e = hipMemcpyAsync(dptr, harr.data(), active.size() * sizeof(TreeDev), hipMemcpyHostToDevice, s);
                 if (e != hipSuccess) { rc = bb::fail(BBH_ERR_HIP, "H2D: %s", hipGetErrorString(e)); break; }
             }
-            if (sys_n > 0) {
-                log_kernel = "sys";
-                const SysDev& S = jobs[active[0]].t->sys;
-                static const bool sys_phases = getenv("BBHIP_SYS_PHASES") != nullptr;
-                if (sys_phases) {
-                    if (all50) hipLaunchKernelGGL((k_tree_sys<KS50, true>), dim3((unsigned)S.G), block, KS50::o.total + sys_lds_bytes<KS50>(), s, dptr, S);
-                    else hipLaunchKernelGGL((k_tree_sys<KS254, true>), dim3((unsigned)S.G), block, KS254::o.total + sys_lds_bytes<KS254>(), s, dptr, S);
-                } else if (all50) hipLaunchKernelGGL(k_tree_sys<KS50>, dim3((unsigned)S.G), block, KS50::o.total + sys_lds_bytes<KS50>(), s, dptr, S);
-                else hipLaunchKernelGGL(k_tree_sys<KS254>, dim3((unsigned)S.G), block, KS254::o.total + sys_lds_bytes<KS254>(), s, dptr, S);
-            } else if (pk != nullptr) {
-                log_kernel = "pipe";
-                static const bool pipe_audit = getenv("BBHIP_PIPE_AUDIT") != nullptr;
-                static const bool pipe_phases = getenv("BBHIP_PIPE_PHASES") != nullptr || pipe_audit;
-                if (pipe_audit) {
-                    static const int audit_mode = std::strcmp(getenv("BBHIP_PIPE_AUDIT"), "corrupt") == 0 ? 2 : 1;
-                    for (size_t a = 0; a < active.size(); ++a) harr[a].audit = audit_mode;
-                    e = hipMemcpyAsync(dptr, harr.data(), active.size() * sizeof(TreeDev), hipMemcpyHostToDevice, s);
-                    if (e != hipSuccess) { rc = bb::fail(BBH_ERR_HIP, "H2D: %s", hipGetErrorString(e)); break; }
-                }
-                // (every instance has its phase-timer / audit twin - ADVICE r4: tolerance-diameter trees used to run unaudited
-                // under BBHIP_PIPE_AUDIT while bbh_tree_stats reported "no difference")
-                hipLaunchKernelGGL(pipe_phases ? pk->fn_prof : pk->fn, grid, block, pk->lds, s, dptr);
-            } else if (fk != nullptr && prof_phases && f_packed) {
-                log_kernel = "fast+phases";
-                if (all50) hipLaunchKernelGGL((k_tree_fast<KF50P, true>), grid, block, fk->lds, s, dptr);
-                else hipLaunchKernelGGL((k_tree_fast<KF254P, true>), grid, block, fk->lds, s, dptr);
-            } else if (fk != nullptr) {
-                log_kernel = "fast";
-                hipLaunchKernelGGL(fk->fn, grid, block, fk->lds, s, dptr);
-            } else if (prof_phases) {
-                if (all50) hipLaunchKernelGGL((k_tree_insert<true, KC50>), grid, block, lds, s, dptr);
-                else hipLaunchKernelGGL((k_tree_insert<true>), grid, block, lds, s, dptr);
-            } else {
-                // the complete engine, shape as run-time values; two workgroups per CU when there are more trees than CUs
-                if (dense_launch(active.size(), lds)) hipLaunchKernelGGL(k_tree_insert_dense<KC>, grid, block, lds, s, dptr);
-                else hipLaunchKernelGGL((k_tree_insert<false, KC>), grid, block, lds, s, dptr);
+
+            // ---- 6. the launch
+            engine = sys_n > 0 ? Engine::Sys : (pk != nullptr ? Engine::Pipe : (fk != nullptr ? Engine::Fast : Engine::Complete));
+            fast_phases = engine == Engine::Fast && env.phases && !fk->buffers;
+            const dim3 grid((unsigned)active.size()), block(TB);
+            switch (engine) {
+                case Engine::Sys: sys_launch(jobs[active[0]].t, dptr, s); break;
+                case Engine::Pipe:
+                    // (every instance has its phase-timer / audit twin - ADVICE r4: tolerance-diameter trees used to run unaudited
+                    // under BBHIP_PIPE_AUDIT while bbh_tree_stats reported "no difference")
+                    hipLaunchKernelGGL((env.pipe_phases || env.pipe_audit != 0) ? pk->fn_prof : pk->fn, grid, block, pk->lds, s, dptr);
+                    break;
+                case Engine::Fast:
+                    if (!fast_phases) hipLaunchKernelGGL(fk->fn, grid, block, fk->lds, s, dptr);
+                    else if (bf == 50) hipLaunchKernelGGL((k_tree_fast<KF50P, true>), grid, block, fk->lds, s, dptr);
+                    else hipLaunchKernelGGL((k_tree_fast<KF254P, true>), grid, block, fk->lds, s, dptr);
+                    break;
+                case Engine::Complete:
+                    // the complete engine, shape as run-time values; two workgroups per CU when there are more trees than CUs
+                    if (env.phases && bf == 50) hipLaunchKernelGGL((k_tree_insert<true, KC50>), grid, block, lds, s, dptr);
+                    else if (env.phases) hipLaunchKernelGGL((k_tree_insert<true>), grid, block, lds, s, dptr);
+                    else if (dense_launch(active.size(), lds)) hipLaunchKernelGGL(k_tree_insert_dense<KC>, grid, block, lds, s, dptr);
+                    else hipLaunchKernelGGL((k_tree_insert<false, KC>), grid, block, lds, s, dptr);
+                    break;
             }
             e = hipGetLastError();
         }
-        if (prof_tok != (size_t)-1)
-            bb::prof_rename(prof_tok, log_kernel[0] == 's' ? "tree_insert/sys" : (log_kernel[0] == 'p' ? "tree_insert/pipe" : (log_kernel[0] == 'f' ? "tree_insert/fast" : "tree_insert/complete")));
+        const EngineLabels& label = kEngineLabels[(int)engine];
+        if (prof_tok != (size_t)-1) bb::prof_rename(prof_tok, label.prof);
+
+        // ---- 7. read back, 8. the pipelined kernel's run-end audit, 9. the launch log
         if (e == hipSuccess) e = hipMemcpyAsync(harr.data(), dptr, active.size() * sizeof(TreeDev), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { rc = bb::fail(BBH_ERR_HIP, "tree_insert: %s", hipGetErrorString(e)); break; }
-        if (log_kernel[0] == 'p' && harr[0].audit) {
+        if (engine == Engine::Pipe && harr[0].audit) {
             unsigned int au = 0;
             (void)hipMemcpyFromSymbol(&au, HIP_SYMBOL(g_pipe_audit), sizeof(au));
             if (au != 0) {
@@ -3329,22 +3259,9 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
                 break;
             }
         }
-        if (launch_log) {
-            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - log_t0).count();
-            uint64_t after[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            long long done = 0;
-            for (size_t a = 0; a < active.size(); ++a) {
-                for (int z = 0; z < 8; ++z) after[z] += harr[a].stats[z];
-                done += harr[a].processed;
-            }
-            const Job& j0 = jobs[active[0]];
-            fprintf(stderr, "[bbhip launch] %s trees=%zu %s crit=%d elems=%lld %.2f ms (%.2f us/elem) calls=%llu rows=%llu merges=%llu appends=%llu "
-                    "leaf_splits=%llu node_splits=%llu stop=%d\n", log_kernel, active.size(), j0.bufs ? (j0.width == 1 ? "buf8" : j0.width == 2 ? "buf16" : "buf32+") : "packed",
-                    j0.t->h.crit, done, ms, done ? 1e3 * ms / (double)done : 0.0, (unsigned long long)(after[0] - log_before[0]),
-                    (unsigned long long)(after[1] - log_before[1]), (unsigned long long)(after[2] - log_before[2]),
-                    (unsigned long long)(after[3] - log_before[3]), (unsigned long long)(after[4] - log_before[4]),
-                    (unsigned long long)(after[5] - log_before[5]), harr[0].stop_reason);
-        }
+        if (env.launch_log) print_launch_log(fast_phases ? label.log_phases : label.log, jobs, active, harr, log_t0);
+
+        // ---- 10. what a shared pipelined launch says about the next one
         if (multi_requested > 0) {
             size_t left_midway = 0;
             for (size_t a = 0; a < active.size(); ++a) left_midway += harr[a].stop_reason == STOP_PIPE_UNSUPPORTED && harr[a].processed > 0;
@@ -3352,6 +3269,8 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
             if (4 * multi_left_midway >= jobs.size()) multi_pipe_ok = false;
             else if (left_midway == 0) multi_chunk = std::min<long long>(2 * multi_chunk, 1ll << 18);
         }
+
+        // ---- 11. every tree: counters, progress, and what its stop reason asks for
         for (size_t a = 0; a < active.size() && rc == BBH_OK; ++a) {
             Job& j = jobs[active[a]];
             bbh_tree* t = j.t;
@@ -3365,89 +3284,23 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
             std::memcpy(h.mlprof, back.mlprof, sizeof(h.mlprof));
             std::memcpy(h.rprof, back.rprof, sizeof(h.rprof));
             j.done += back.processed;
-            {
-                const bool was_sys = log_kernel[0] == 's';
-                const int kk = (log_kernel[0] == 'p' || was_sys) ? 0 : (log_kernel[0] == 'f' ? 1 : 2);  // (the systolic kernel counts with the pipelined ones)
-                t->kcount[kk] += (uint64_t)back.processed;
-                t->kcount[3 + kk] += 1;
-                if (was_sys) {
-                    // (ids in the sequential engines' order: bb_tree_sys.inc, "BitFeature ids in the reference's order")
-                    if (back.stop_reason != STOP_INTERNAL && back.ctr[C_IDS] > sys_ids_before)
-                        rc = sys_renumber(t, back.out_leaf, (uint32_t)back.processed, sys_ids_before, back.ctr[C_IDS] - sys_ids_before, s);
-                    if (rc != BBH_OK) break;
-                    t->syscount[0] += (uint64_t)back.processed;
-                    t->syscount[1] += 1;
-                    if (back.stop_reason == STOP_SYS_RELAUNCH) t->syscount[2] += 1;
-                    t->syscount[3] = (uint64_t)t->sys.G;
-                    std::vector<unsigned long long> busy((size_t)t->sys.G);
-                    if (hipMemcpy(busy.data(), t->sys.busy, busy.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                        for (unsigned long long b : busy) t->syscount[4] += b;
-                        t->syscount[5] += busy[0];
-                        unsigned long long mx = 0;
-                        for (size_t q = 1; q < busy.size(); ++q) mx = std::max(mx, busy[q]);
-                        t->syscount[6] += mx;
-                    } else {
-                        (void)hipGetLastError();
-                    }
-                    if (back.stop_reason == STOP_SYS_UNSUPPORTED) t->syscount[7] += 1;
-                    {
-                        static const bool sys_dbg_log = getenv("BBHIP_SYS_DEBUG") != nullptr;
-                        uint32_t stale = 0;
-                        if (sys_dbg_log && hipMemcpy(&stale, t->sys.ctl + SC_STALE_CTL, 4, hipMemcpyDeviceToHost) == hipSuccess && stale != 0)
-                            fprintf(stderr, "[bbhip sys state] launch %u: %u polls saw a control word that a read-modify-write read did not, %u saw another launch's FINISH\n", t->sys.launch_id, stale & 0xFFFFu, stale >> 16);
-                    }
-                    static const bool sys_phases_log = getenv("BBHIP_SYS_PHASES") != nullptr;
-                    if (sys_phases_log && back.processed > 0) {
-                        // (phase-timer instance) cycles per element of the internal step: the root's owner, and the busiest owner of every other level
-                        std::vector<unsigned long long> ph((size_t)t->sys.G * 13);
-                        if (hipMemcpy(ph.data(), t->sys.busy, ph.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                            static const char* names[12] = {"lookup", "compare(hit)", "fill+compare(miss)", "guard", "send", "commit", "rest", "misses", "mailbox-rereads", "reread-spins", "ALONE", "ALONE-wait-cycles"};
-                            for (int l = 0; l < t->sys.levels; ++l) {
-                                int best = t->sys.lvl_first[l];
-                                for (int w = t->sys.lvl_first[l]; w < t->sys.lvl_first[l] + t->sys.lvl_count[l]; ++w)
-                                    if (ph[(size_t)w] > ph[(size_t)best]) best = w;
-                                fprintf(stderr, "[bbhip sys phases] level %d: %d workgroups, busiest wg %d: busy %.0f cycles per launch element (%lld elements)", l, t->sys.lvl_count[l], best,
-                                        (double)ph[(size_t)best] / (double)back.processed, (long long)back.processed);
-                                if (l < t->sys.levels - 1)
-                                    for (int i = 0; i < 12; ++i) fprintf(stderr, " %s %.0f", names[i], (double)ph[(size_t)t->sys.G + (size_t)best * 12 + i] / ((i >= 7 && i <= 10) ? 1.0 : (double)back.processed));
-                                fprintf(stderr, "\n");
-                            }
-                        } else {
-                            (void)hipGetLastError();
-                        }
-                    }
-                }
-                if (back.stop_reason == STOP_PIPE_UNSUPPORTED) t->kcount[6] += 1;
-                if (back.stop_reason == STOP_NODES || back.stop_reason == STOP_CF8 || back.stop_reason == STOP_CF16 || back.stop_reason == STOP_CF32) t->kcount[7] += 1;
+            t->kcount[label.kcol] += (uint64_t)back.processed;
+            t->kcount[3 + label.kcol] += 1;
+            if (engine == Engine::Sys) {
+                rc = sys_after_launch(t, back, s);
+                if (rc != BBH_OK) break;
             }
+            const bool pool_stop = back.stop_reason == STOP_NODES || back.stop_reason == STOP_CF8 || back.stop_reason == STOP_CF16 || back.stop_reason == STOP_CF32;
+            if (back.stop_reason == STOP_PIPE_UNSUPPORTED) t->kcount[6] += 1;
+            if (pool_stop) t->kcount[7] += 1;
             if (j.old_left > 0) j.old_left = std::max<int64_t>(0, j.old_left - back.processed);
-            if (t->sys_off_left > 0 && log_kernel[0] != 's') t->sys_off_left = std::max<int64_t>(0, t->sys_off_left - back.processed);
+            if (t->sys_off_left > 0 && engine != Engine::Sys) t->sys_off_left = std::max<int64_t>(0, t->sys_off_left - back.processed);
             if (prof_tok != (size_t)-1) bb::prof_units(prof_tok, back.processed);  // elements this launch inserted
             j.stalls = (back.processed == 0 && back.stop_reason != STOP_PIPE_UNSUPPORTED && back.stop_reason != STOP_PIPE_NEEDS_ML) ? j.stalls + 1 : 0;
             if (j.stalls > 3) { rc = bb::fail(BBH_ERR_CAPACITY, "tree engine made no progress (stop reason %d)", back.stop_reason); break; }
-            const int64_t left = j.n - j.done;
-            // what a pool that ran out is grown to: half as much again, or what the elements that are left are expected to
-            // need (pregrow's rates) if that is more
-            uint64_t uleft_for_nodes = 0;
-            auto more = [&](uint32_t used, uint32_t cap, uint64_t expect) -> uint32_t {
-                if (tiny_pools()) return clamp30((uint64_t)cap + 8 + 2 * (uint64_t)h.ctr[C_DEPTH]);  // (one insertion's worst case fits)
-                return clamp30(std::max<uint64_t>((uint64_t)cap + 1, (uint64_t)used + expect));  // (grow_cf takes the larger of this and its geometric step)
-            };
-            const uint64_t nblk = node_blocks((uint32_t)h.bf + 1);
-            // (nodes: blocks; a pool that is compacted on the way - grow_nodes - takes `want - used` as the room asked for)
-            auto more_nodes = [&]() -> uint32_t {
-                if (tiny_pools()) return clamp30((uint64_t)h.ctr[C_NODES] + (8 + 2 * (uint64_t)h.ctr[C_DEPTH]) * nblk);
-                const uint64_t expect = (uleft_for_nodes / (uint64_t)std::max(1, h.bf / 2) + 64) * nblk;
-                return clamp30(std::max<uint64_t>((uint64_t)h.cap_nodes + h.cap_nodes / 2, (uint64_t)h.ctr[C_NODES] + expect));
-            };
-            const uint64_t uleft = (uint64_t)std::max<int64_t>(left, 0);
-            uleft_for_nodes = uleft;
             switch (back.stop_reason) {
                 case STOP_DONE: break;
-                case STOP_NODES: rc = grow_nodes(t, more_nodes(), tiny_pools() ? (8 + 2 * (uint64_t)h.ctr[C_DEPTH]) * nblk : (uleft / (uint64_t)std::max(1, h.bf / 2) + 64) * nblk); break;
-                case STOP_CF8: rc = grow_cf(t, 0, more(h.ctr[C_N8], h.cap8, uleft / 8 + 1024)); break;
-                case STOP_CF16: rc = grow_cf(t, 1, more(h.ctr[C_N16], h.cap16, (j.width == 2 ? uleft : uleft / 64) + 64)); break;
-                case STOP_CF32: rc = grow_cf(t, 2, more(h.ctr[C_N32], h.cap32, uleft / (uint64_t)std::max(1, h.bf / 6) + 256)); break;
+                case STOP_NODES: case STOP_CF8: case STOP_CF16: case STOP_CF32: rc = grow_after_stop(t, j, back, j.n - j.done); break;
                 case STOP_DEPTH: rc = bb::fail(BBH_ERR_CAPACITY, "tree deeper than %d levels (or corrupt link)", MAXD); break;
                 case STOP_RANGE: rc = bb::fail(BBH_ERR_INVALID, "n_samples exceeds 2^32-1 (engine limit)"); break;
                 case STOP_PIPE_UNSUPPORTED:
@@ -3464,96 +3317,10 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
                 case STOP_SYS_UNSUPPORTED: t->sys_off_left = 1 << 16; break;
                 case STOP_PIPE_NEEDS_ML: t->pipe_ml = true; break;  // relaunched at once, with the multi-level instance
                 case STOP_PIPE_PREFERS_SL: t->pipe_ml = false; break;  // ... and back (after a stint of >= PIPE_ML_STINT elements)
-                case STOP_INTERNAL: {
-                    if (log_kernel[0] == 's') {
-                        uint32_t dbg[16] = {0};
-                        (void)hipMemcpy(dbg, t->sys.ctl, sizeof(dbg), hipMemcpyDeviceToHost);
-                        rc = bb::fail(BBH_ERR_HIP, "level-systolic kernel: internal error at bb_tree_sys.inc:%u (node %u child %u sent %u acked %u | fresh sent %u acked %u | level/miss/row %#x element %u)",
-                                      back.giveup_line, dbg[8], dbg[9], dbg[10], dbg[11], dbg[12], dbg[13], dbg[14], dbg[15]);
-                        if (getenv("BBHIP_SYS_DEBUG")) {  // where every workgroup was waiting
-                            std::vector<unsigned long long> stw((size_t)t->sys.G * 15);
-                            if (hipMemcpy(stw.data(), t->sys.busy, stw.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                                for (int w = 0; w < t->sys.G; ++w) {
-                                    const unsigned long long a = stw[(size_t)t->sys.G * 13 + (size_t)w * 2], b = stw[(size_t)t->sys.G * 13 + (size_t)w * 2 + 1];
-                                    const unsigned kind = (unsigned)(a >> 32);
-                                    if (kind != 4)
-                                        fprintf(stderr, "[bbhip sys state] wg %d: %s node %u child %u want %u (owner index of child in the next level: %u)\n", w,
-                                                kind == 1 ? "guard (pending below the child)" : kind == 2 ? "ALONE (waits for the child)" : kind == 3 ? "drain (all children)" : kind == 5 ? "in an internal step (node, element, alone)" : kind == 6 ? "in a leaf step (node, element, alone)" : "busy / never polled",
-                                                (unsigned)a, (unsigned)(b >> 32), (unsigned)b, (unsigned)(((unsigned)(b >> 32)) / node_blocks((uint32_t)t->h.bf + 1)));
-                                    if (kind >= 1 && kind <= 3) {  // the words the wait is about, as the host sees them now
-                                        auto words = [&](uint32_t nd, const char* what) {
-                                            unsigned long long mw = 0, upw = 0; uint32_t sw = 0, le = 0; NodeHdr hd{};
-                                            if (nd >= t->h.cap_nodes) return;
-                                            (void)hipMemcpy(&mw, t->sys.mail + nd, 8, hipMemcpyDeviceToHost);
-                                            (void)hipMemcpy(&upw, t->sys.up + nd, 8, hipMemcpyDeviceToHost);
-                                            (void)hipMemcpy(&sw, t->sys.sent + nd, 4, hipMemcpyDeviceToHost);
-                                            (void)hipMemcpy(&le, t->sys.laste + nd, 4, hipMemcpyDeviceToHost);
-                                            (void)hipMemcpy(&hd, t->h.node_hdr + nd, sizeof(hd), hipMemcpyDeviceToHost);
-                                            fprintf(stderr, "[bbhip sys state]     %s %u: mail acked %u len %u res %u epoch %u | sent %u | last element+1 %u | up (node %u row %u) | hdr len %u leaf %#x\n", what, nd,
-                                                    (unsigned)mw, (unsigned)((mw >> 32) & 0xFFFF), (unsigned)((mw >> 48) & 3), (unsigned)(mw >> 50), sw, le, (unsigned)(upw >> 32), (unsigned)upw, hd.len, hd.leaf);
-                                        };
-                                        words((unsigned)a, "node");
-                                        words((unsigned)(b >> 32), "child");
-                                        {   // where the tree (as the host sees it now) holds the child, and the node's first rows
-                                            const uint32_t used = std::min<uint32_t>(t->h.cap_nodes, 1u << 22), nblk_ = node_blocks((uint32_t)t->h.bf + 1);
-                                            std::vector<uint32_t> lk((size_t)used * NG);
-                                            std::vector<NodeHdr> hh(used);
-                                            if (hipMemcpy(lk.data(), t->h.node_link, lk.size() * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-                                                hipMemcpy(hh.data(), t->h.node_hdr, hh.size() * sizeof(NodeHdr), hipMemcpyDeviceToHost) == hipSuccess) {
-                                                const uint32_t nd_ = (unsigned)a, ch_ = (unsigned)(b >> 32);
-                                                if (nd_ < used) {
-                                                    fprintf(stderr, "[bbhip sys state]     node %u rows' children:", nd_);
-                                                    for (uint32_t r = 0; r < hh[nd_].len && r < 6; ++r) fprintf(stderr, " %u", lk[(size_t)nd_ * NG + r]);
-                                                    fprintf(stderr, "\n");
-                                                }
-                                                for (uint32_t x = 0; x + nblk_ <= used; ++x) {
-                                                    if ((hh[x].leaf & HW_LEAF) || hh[x].len == 0 || hh[x].len > (uint32_t)t->h.bf + 1 || hw_cap(hh[x].leaf) != (uint32_t)t->h.bf + 1) continue;
-                                                    for (uint32_t r = 0; r < hh[x].len; ++r)
-                                                        if (lk[(size_t)x * NG + r] == ch_) fprintf(stderr, "[bbhip sys state]     child %u is row %u of node %u (len %u)\n", ch_, r, x, hh[x].len);
-                                                }
-                                            }
-                                        }
-                                        if (kind == 3) {
-                                            NodeHdr hd{};
-                                            (void)hipMemcpy(&hd, t->h.node_hdr + (unsigned)a, sizeof(hd), hipMemcpyDeviceToHost);
-                                            for (uint32_t r = 0; r < hd.len && r <= (uint32_t)t->h.bf; ++r) {
-                                                uint32_t ch = 0, sw = 0; unsigned long long mw = 0;
-                                                (void)hipMemcpy(&ch, t->h.node_link + (size_t)(unsigned)a * NG + r, 4, hipMemcpyDeviceToHost);
-                                                if (ch >= t->h.cap_nodes) continue;
-                                                (void)hipMemcpy(&sw, t->sys.sent + ch, 4, hipMemcpyDeviceToHost);
-                                                (void)hipMemcpy(&mw, t->sys.mail + ch, 8, hipMemcpyDeviceToHost);
-                                                if ((uint32_t)mw != sw) words(ch, "  behind: row's child");
-                                            }
-                                        }
-                                    }
-                                }
-                                {   // ring positions: what a producer sent and its consumer has not taken
-                                    std::vector<uint32_t> pos((size_t)t->sys.G * 2 * SYS_MAXPROD);
-                                    if (hipMemcpy(pos.data(), (const uint8_t*)t->sys.busy + (size_t)t->sys.G * 15 * 8, pos.size() * 4, hipMemcpyDeviceToHost) == hipSuccess) {
-                                        for (int l = 0; l + 1 < t->sys.levels; ++l)
-                                            for (int p = 0; p < t->sys.lvl_count[l]; ++p)
-                                                for (int q = 0; q < t->sys.lvl_count[l + 1]; ++q) {
-                                                    const int pw = t->sys.lvl_first[l] + p, cw = t->sys.lvl_first[l + 1] + q;
-                                                    const uint32_t tail = pos[(size_t)pw * 2 * SYS_MAXPROD + SYS_MAXPROD + q], head = pos[(size_t)cw * 2 * SYS_MAXPROD + p];
-                                                    if (tail != head) {
-                                                        unsigned long long ab[2] = {0, 0};
-                                                        (void)hipMemcpy(ab, t->sys.rings + (((size_t)cw * SYS_MAXPROD + (size_t)p) * SYS_R + (head & (SYS_R - 1u))) * 2, 16, hipMemcpyDeviceToHost);
-                                                        fprintf(stderr, "[bbhip sys state] ring wg %d -> wg %d: sent %u taken %u; the slot the consumer is looking at: %016llx %016llx (launch id %u: gen %u alone %u node %u element %u | gen %u launch %u epoch %u)\n",
-                                                                pw, cw, tail, head, ab[0], ab[1], t->sys.launch_id, (unsigned)(ab[0] >> 63), (unsigned)((ab[0] >> 62) & 1), (unsigned)((ab[0] >> 31) & 0x3FFFFFFF),
-                                                                (unsigned)(ab[0] & 0x7FFFFFFF), (unsigned)(ab[1] >> 63), (unsigned)((ab[1] >> 32) & 0x7FFFFFFF), (unsigned)ab[1]);
-                                                    }
-                                                }
-                                    }
-                                }
-                                for (int l = 0; l < t->sys.levels; ++l) fprintf(stderr, "[bbhip sys state] level %d: workgroups %d..%d\n", l, t->sys.lvl_first[l], t->sys.lvl_first[l] + t->sys.lvl_count[l] - 1);
-                            }
-                        }
-                        break;
-                    }
-                    const unsigned int line = back.giveup_line;
-                    rc = bb::fail(BBH_ERR_HIP, "pipelined kernel: a wait gave up (internal error; first at bb_tree_pipe.inc:%u)", line);
+                case STOP_INTERNAL:
+                    rc = engine == Engine::Sys ? sys_internal_error(t, back)
+                                               : bb::fail(BBH_ERR_HIP, "pipelined kernel: a wait gave up (internal error; first at bb_tree_pipe.inc:%u)", (unsigned int)back.giveup_line);
                     break;
-                }
                 default: rc = bb::fail(BBH_ERR_HIP, "unknown stop reason %d", back.stop_reason); break;
             }
         }
@@ -3884,8 +3651,7 @@ extern "C" int bbh_tree_fit_buffers(bbh_tree* t, const void* bufs, int32_t width
     const size_t row_bytes = ((size_t)t->h.F + 1) * width;
     bb::DevOut o;
     BB_TRY(o.init(out_leaf, (size_t)k * 4));
-    static const bool no_singleton_path = getenv("BBHIP_NO_SINGLETON_PATH") != nullptr;
-    const bool split_runs = width == 1 && !no_singleton_path;
+    const bool split_runs = width == 1 && !tree_env().no_singleton_path;
     if (bb::is_device_ptr(bufs)) {
         if (split_runs) {
             // the n_samples column: gathered on the device, one contiguous copy (a 1-byte-wide hipMemcpy2D over
@@ -4134,56 +3900,14 @@ extern "C" int bbh_tree_stats(bbh_tree* t, uint64_t* out8) {
     if (!t || !out8) return bb::fail(BBH_ERR_INVALID, "null argument");
     for (int i = 0; i < 7; ++i) out8[i] = t->h.stats[i];
     out8[7] = t->h.ctr[C_IDS];
-    if (getenv("BBHIP_PIPE_AUDIT")) {
+    const TreeEnv& env = tree_env();
+    if (env.pipe_audit != 0) {
         unsigned long long runs = 0;
         (void)hipMemcpyFromSymbol(&runs, HIP_SYMBOL(g_pipe_audit_runs), sizeof(runs));
         fprintf(stderr, "[bbhip pipe audit] %llu slots audited at run ends so far (this process), no difference\n", runs);
     }
-    if (getenv("BBHIP_PIPE_PHASES")) {
-        static const char* nm[16] = {"router:setup", "router:wait", "router:compare", "router:commit", "router:drain", "leaf:wait", "leaf:fill",
-                                     "leaf:compare", "leaf:cf+dot", "leaf:decide+apply", "all:flush", "all:cold", "#runs", "#router-stale", "#leaf-pre-hits", "#leaf-stale"};
-        const double n = (double)(t->h.stats[2] + t->h.stats[3]);
-        fprintf(stderr, "[bbhip pipe phases, per insert]");
-        for (int i = 0; i < 16; ++i) fprintf(stderr, " %s=%.*f", nm[i], i < 12 ? 0 : 4, n > 0 ? (double)t->h.phase[i] / n : 0.0);
-        static const char* kd[3] = {"pre-compared, best row folded", "own", "pre-compared, every row checked"};
-        fprintf(stderr, "\n[bbhip pipe leaf compares]");
-        for (int i = 0; i < 3; ++i)
-            fprintf(stderr, " %s: %.3f/insert x %.0f cycles", kd[i], n > 0 ? (double)t->h.sphase[2 * i + 1] / n : 0.0,
-                    t->h.sphase[2 * i + 1] ? (double)t->h.sphase[2 * i] / (double)t->h.sphase[2 * i + 1] : 0.0);
-        fprintf(stderr, "\n");
-        fprintf(stderr, "[bbhip pipe router waits, per insert] ring entry %.0f, row + pre-compare of wave 2 %.0f, pending jobs of a nearly full leaf %.0f, "
-                "decision on a full leaf %.0f\n", n > 0 ? (double)t->h.rprof[0] / n : 0.0, n > 0 ? (double)t->h.rprof[1] / n : 0.0,
-                n > 0 ? (double)t->h.rprof[2] / n : 0.0, n > 0 ? (double)t->h.rprof[3] / n : 0.0);
-        if (t->h.splitprof[8]) {
-            const double ns = (double)t->h.splitprof[8];
-            fprintf(stderr, "[bbhip pipe leaf splits] %.4f/insert x %.0f cycles:", n > 0 ? ns / n : 0.0, (double)t->h.splitprof[9] / ns);
-            for (int i = 0; i < 8; ++i) fprintf(stderr, " s%d=%.0f", i, (double)t->h.splitprof[i] / ns);
-            fprintf(stderr, "\n");
-        }
-        if (t->pipe_ml)
-            fprintf(stderr, "[bbhip pipe multi-level router] upper-slot fills %.3f/insert x %.0f cycles; tracking levels committed %.3f/insert, "
-                    "cluster-feature cache misses %.3f/insert; router waiting for a level's update by a helper wave %.0f cycles/insert, for "
-                    "all of them and their stores (before a fill) %.0f; of a fill: loads %.0f cycles, slot + corrections %.0f\n", n > 0 ? (double)t->h.sphase[7] / n : 0.0,
-                    t->h.sphase[7] ? (double)t->h.sphase[6] / (double)t->h.sphase[7] : 0.0, n > 0 ? (double)t->h.mlprof[1] / n : 0.0,
-                    n > 0 ? (double)t->h.mlprof[0] / n : 0.0, n > 0 ? (double)t->h.mlprof[2] / n : 0.0, n > 0 ? (double)t->h.mlprof[3] / n : 0.0,
-                    t->h.sphase[7] ? (double)t->h.mlprof[4] / (double)t->h.sphase[7] : 0.0, t->h.sphase[7] ? (double)t->h.mlprof[5] / (double)t->h.sphase[7] : 0.0);
-    }
-    if (getenv("BBHIP_PHASES")) {
-        fprintf(stderr, "[bbhip phases, cycles/insert]");
-        const double n = (double)(t->h.stats[2] + t->h.stats[3]);
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " p%d=%.0f", i, n > 0 ? (double)t->h.phase[i] / n : 0.0);
-        static const char* cls[3] = {"fill/miss", "tag-only", "compare"};  // (k_tree_fast; k_tree_insert: miss, zero-skip, mirror-hit)
-        fprintf(stderr, "\n[bbhip p0 detail] loop-top barrier+checks=%.0f wait-for-prefetched-row=%.0f", n > 0 ? (double)t->h.phase[14] / n : 0.0,
-                n > 0 ? (double)t->h.phase[15] / n : 0.0);
-        for (int i = 0; i < 3; ++i)
-            fprintf(stderr, "\n[bbhip descent] %-10s levels/insert=%.3f cycles/level=%.0f", cls[i],
-                    n > 0 ? (double)t->h.phase[11 + i] / n : 0.0,
-                    t->h.phase[11 + i] ? (double)t->h.phase[8 + i] / (double)t->h.phase[11 + i] : 0.0);
-        fprintf(stderr, "\n[bbhip split phases, cycles/split]");
-        const double ns = (double)t->h.stats[4];
-        for (int i = 0; i < 8; ++i) fprintf(stderr, " s%d=%.0f", i, ns > 0 ? (double)t->h.sphase[i] / ns : 0.0);
-        fprintf(stderr, "\n");
-    }
+    if (env.pipe_phases) print_pipe_phases(t);
+    if (env.phases) print_phases(t);
     return BBH_OK;
 }
 

@@ -3,7 +3,7 @@
 Tanimoto kernel on rows in pinned host memory (the PCIe-inclusive rate - never the bench's `value`).
     python tools/ingest.py [rows]"""
 import os, sys, time, tempfile
-os.environ.pop("BBHIP_LAUNCH_LOG", None)  # (any value, "0" included, turns the log on)
+os.environ.pop("BBHIP_LAUNCH_LOG", None)  # (any value but the empty one and "0" turns the log on)
 sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
 import numpy as np
 import torch

@@ -1,7 +1,7 @@
 """HIP engine (pipelined kernel by default) against the CPU oracle, element by element, on the bench workloads.
     python tools/pipe_check.py [rows] [bf ...]"""
 import os, sys, time
-os.environ.pop("BBHIP_LAUNCH_LOG", None)  # (any value, "0" included, turns the log on)
+os.environ.pop("BBHIP_LAUNCH_LOG", None)  # (any value but the empty one and "0" turns the log on)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
