@@ -391,21 +391,6 @@ int forced_kernel() {
     return 0;
 }
 
-struct Scratch {  // device blocks of one call, returned to the cache on every exit path
-    std::vector<void*> blocks;
-    template <typename T>
-    hipError_t get(T** p, size_t bytes) {
-        void* v = nullptr;
-        hipError_t e = bb::dev_alloc(&v, bytes ? bytes : 4);
-        if (e == hipSuccess) blocks.push_back(v);
-        *p = (T*)v;
-        return e;
-    }
-    ~Scratch() {
-        for (void* b : blocks) bb::dev_free(b);
-    }
-};
-
 }  // namespace
 
 extern "C" int bbh_jt_assign(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* cents, int64_t nc,
@@ -437,7 +422,7 @@ extern "C" int bbh_jt_assign(const uint8_t* queries, int64_t nq, int64_t q_strid
     const bool use_mfma = forced == 2 || (forced == 0 && mfma_ok && nc >= 64 && nq >= 64);
     const int cus = cu_count();
 
-    Scratch tmp;
+    bb::DevScope tmp(s);
     uint32_t *ccard = nullptr, *qcard = nullptr;
     BB_HIP(tmp.get(&ccard, (size_t)nc * 4));
     BB_TRY(bbh_popcount_rows(cd, nc, nbytes, nbytes, ccard, s));
@@ -497,9 +482,7 @@ extern "C" int bbh_jt_assign(const uint8_t* queries, int64_t nq, int64_t q_strid
     BB_TRY(oi.finish(s));
     BB_TRY(on.finish(s));
     BB_TRY(ou.finish(s));
-    // (the scratch blocks go back to the cache when this returns: the stream must be done with them)
-    BB_HIP(hipStreamSynchronize(s));
-    return BBH_OK;
+    return tmp.sync();
 }
 
 extern "C" int bbh_jt_dist_matrix(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* cents,
@@ -519,7 +502,7 @@ extern "C" int bbh_jt_dist_matrix(const uint8_t* queries, int64_t nq, int64_t q_
     const bool al4 = (uintptr_t)qd % 4 == 0 && (uintptr_t)cd % 4 == 0 && q_stride % 4 == 0;
     const bool fast = al4 && (nbytes == 8 || nbytes == 16 || nbytes == 32 || nbytes == 64 || nbytes == 128 ||
                               nbytes == 256);
-    Scratch tmp;
+    bb::DevScope tmp(s);
     {
         bb::ProfScope ps("jt_dist_matrix", s);
         ps.units(nq);
@@ -551,8 +534,7 @@ extern "C" int bbh_jt_dist_matrix(const uint8_t* queries, int64_t nq, int64_t q_
         BB_HIP(hipGetLastError());
     }
     BB_TRY(o.finish(s));
-    BB_HIP(hipStreamSynchronize(s));
-    return BBH_OK;
+    return tmp.sync();
 }
 
 // test hook of the operand-map probe: a (16 x 64 int8), b (64 x 16 int8), d (16 x 16 int32), host or device

@@ -64,6 +64,11 @@ int ensure_device();  // picks device 0 lazily, checks it is gfx950
 // multiround round creates hundreds of trees, so blocks are recycled by size class instead of
 // being returned to the driver (bbh_trim_cache releases them): blocks of up to 64 MiB, at most BBHIP_CACHE_MB (default 4 GiB)
 // per process; larger blocks go straight back to the driver.
+//
+// The rule of the cache: dev_free hands a block to whichever thread asks dev_alloc for that size next, at once.  A block may
+// therefore go back only when the stream that used it has been synchronised - on the error paths too, where kernels that
+// were launched before the failing call may still be running.  DevScope (below) enforces that for the blocks of one call;
+// the long-lived blocks of a tree are freed by their owner after it has synchronised.
 // ---------------------------------------------------------------------------------------
 hipError_t dev_alloc(void** p, size_t bytes);
 void dev_free(void* p);
@@ -126,6 +131,47 @@ struct DevOut {
     }
     ~DevOut() {
         if (owned) dev_free(owned);
+    }
+};
+
+// The device and pinned blocks of one call, bound to the call's stream.  Every block it handed out goes back on every exit
+// path, and not before the stream is done with it: a call ends in sync(); a return that comes before that - BB_HIP / BB_TRY
+// after kernels were launched - makes the destructor synchronise first.  Declare it after the call's DevIn / DevOut: it is
+// destroyed before them, so their blocks are covered by the same synchronisation.
+class DevScope {
+    struct Block { void* p; bool pinned; };
+    hipStream_t s_;
+    std::vector<Block> blocks_;
+    bool synced_ = false;  // a sync() has succeeded since the last block was handed out
+    hipError_t keep(void** p, hipError_t e, bool pinned) {
+        if (e != hipSuccess) { *p = nullptr; return e; }
+        blocks_.push_back({*p, pinned});
+        synced_ = false;
+        return e;
+    }
+
+public:
+    explicit DevScope(hipStream_t s) : s_(s) {}
+    DevScope(const DevScope&) = delete;
+    DevScope& operator=(const DevScope&) = delete;
+    template <class T>
+    hipError_t get(T** p, size_t bytes) {  // a block of the caching allocator (never of size 0)
+        return keep((void**)p, dev_alloc((void**)p, bytes ? bytes : 4), false);
+    }
+    template <class T>
+    hipError_t pinned(T** p, size_t bytes) {  // page-locked host memory
+        return keep((void**)p, hipHostMalloc((void**)p, bytes, hipHostMallocDefault), true);
+    }
+    // the synchronisation that closes a call (or a stage of it); `what` starts the message of a failure
+    int sync(const char* what = "hipStreamSynchronize(s) failed") {
+        const hipError_t e = hipStreamSynchronize(s_);
+        if (e != hipSuccess) return fail(BBH_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+        synced_ = true;
+        return BBH_OK;
+    }
+    ~DevScope() {
+        if (!blocks_.empty() && !synced_) (void)hipStreamSynchronize(s_);
+        for (const Block& b : blocks_) b.pinned ? (void)hipHostFree(b.p) : dev_free(b.p);
     }
 };
 

@@ -516,8 +516,9 @@ extern "C" int bbh_jt_best_match(const uint8_t* queries, int64_t nq, const uint8
     BB_TRY(on.init(out_inter, (size_t)nq * 4));
     BB_TRY(ou.init(out_union, (size_t)nq * 4));
     BB_TRY(os.init(out_sims, (size_t)nq * (size_t)nc * 8));
+    bb::DevScope tmp(s);
     uint32_t* ccard = nullptr;
-    BB_HIP(bb::dev_alloc(&ccard, (size_t)nc * 4));
+    BB_HIP(tmp.get(&ccard, (size_t)nc * 4));
     int rc = launch_arr_vec<false>((const uint8_t*)c.dev, nc, nbytes, nbytes, nullptr, nullptr, nullptr,
                                    nullptr, nullptr, ccard, s);
     if (rc == BBH_OK && nq > 0) {
@@ -540,9 +541,7 @@ extern "C" int bbh_jt_best_match(const uint8_t* queries, int64_t nq, const uint8
     if (rc == BBH_OK) rc = on.finish(s);
     if (rc == BBH_OK) rc = ou.finish(s);
     if (rc == BBH_OK) rc = os.finish(s);
-    hipError_t e = hipStreamSynchronize(s);
-    bb::dev_free(ccard);
-    if (rc == BBH_OK && e != hipSuccess) rc = bb::fail(BBH_ERR_HIP, "best_match: %s", hipGetErrorString(e));
+    if (rc == BBH_OK) rc = tmp.sync("best_match");
     return rc;
 }
 
@@ -795,17 +794,16 @@ static int isim_dev(const void* ls_dev, int width, int64_t nf, int64_t n_objects
         *out_host = NAN;
         return BBH_OK;
     }
+    bb::DevScope tmp(s);
     double* d = nullptr;
-    BB_HIP(bb::dev_alloc(&d, 8));
+    BB_HIP(tmp.get(&d, 8));
     {
         bb::ProfScope ps("isim_from_sum", s);
         hipLaunchKernelGGL(k_isim_from_sum, dim3(1), dim3(256), 0, s, ls_dev, width, nf, (long long)n_objects, d);
     }
-    hipError_t e = hipMemcpyAsync(out_host, d, 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    bb::dev_free(d);
+    const hipError_t e = hipMemcpyAsync(out_host, d, 8, hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) return bb::fail(BBH_ERR_HIP, "isim_from_sum: %s", hipGetErrorString(e));
-    return BBH_OK;
+    return tmp.sync("isim_from_sum");
 }
 
 extern "C" int bbh_isim_from_sum(const void* linear_sum, int32_t ls_width, int64_t n_features,
@@ -829,13 +827,11 @@ extern "C" int bbh_isim_rows(const uint8_t* arr, int64_t n, int64_t n_cols, int 
     hipStream_t s = (hipStream_t)stream;
     bb::DevIn a;
     BB_TRY(a.init(arr, (size_t)(n * n_cols), s));
+    bb::DevScope tmp(s);  // (no sync() of its own: isim_dev makes the call's, the destructor one more as before)
     unsigned long long* ls = nullptr;
-    BB_HIP(bb::dev_alloc(&ls, (size_t)n_features * 8));
-    int rc = add_rows_dev((const uint8_t*)a.dev, n, n_cols, packed, n_features, ls, s);
-    if (rc == BBH_OK) rc = isim_dev(ls, 8, n_features, n, out, warn, s);
-    (void)hipStreamSynchronize(s);
-    bb::dev_free(ls);
-    return rc;
+    BB_HIP(tmp.get(&ls, (size_t)n_features * 8));
+    BB_TRY(add_rows_dev((const uint8_t*)a.dev, n, n_cols, packed, n_features, ls, s));
+    return isim_dev(ls, 8, n_features, n, out, warn, s);
 }
 
 // =======================================================================================
@@ -900,8 +896,9 @@ extern "C" int bbh_isim_pair_min_gap(const uint64_t* sums, const uint64_t* sizes
     BB_TRY(dsizes.init(sizes, (size_t)k * 8, s));
     BB_TRY(d1.init(h1.data(), (size_t)k * 8, s));
     BB_TRY(d2.init(h2.data(), (size_t)k * 8, s));
+    bb::DevScope tmp(s);
     unsigned long long* dout = nullptr;
-    BB_HIP(bb::dev_alloc(&dout, 8));
+    BB_HIP(tmp.get(&dout, 8));
     const unsigned long long one = 0x3FF0000000000000ull;
     int rc = BBH_OK;
     do {
@@ -925,9 +922,7 @@ extern "C" int bbh_isim_pair_min_gap(const uint64_t* sums, const uint64_t* sizes
         if (e != hipSuccess) { rc = bb::fail(BBH_ERR_HIP, "D2H: %s", hipGetErrorString(e)); break; }
         std::memcpy(out, &bits, 8);
     } while (false);
-    (void)hipStreamSynchronize(s);
-    bb::dev_free(dout);
-    return rc;
+    return rc;  // (the scope synchronises once more, as this call always did, before the staged inputs go)
 }
 
 // =======================================================================================
@@ -981,13 +976,14 @@ extern "C" int bbh_most_dissimilar(const uint8_t* Y, int64_t n, int64_t nbytes, 
     BB_TRY(o1.init(sims1, (size_t)n * 8));
     BB_TRY(o2.init(sims2, (size_t)n * 8));
     const uint8_t* yd = (const uint8_t*)y.dev;
+    bb::DevScope tmp(s);
     void* scratch = nullptr;
     const size_t rowb = ((size_t)nbytes + 15) / 16 * 16;
     const size_t sz_ls = (size_t)nbytes * 8 * 8, sz_card = (size_t)n * 4, sz_sim = (size_t)n * 8;
     const size_t off_cen = sz_ls, off_r1 = off_cen + rowb, off_r2 = off_r1 + rowb, off_idx = off_r2 + rowb;
     const size_t off_card = off_idx + 16;
     const size_t off_sim = (off_card + sz_card + 15) / 16 * 16;
-    BB_HIP(bb::dev_alloc(&scratch, off_sim + 2 * sz_sim));
+    BB_HIP(tmp.get(&scratch, off_sim + 2 * sz_sim));
     auto* ls = (unsigned long long*)scratch;
     auto* cen = (uint8_t*)scratch + off_cen;
     auto* row1 = (uint8_t*)scratch + off_r1;
@@ -1023,9 +1019,7 @@ extern "C" int bbh_most_dissimilar(const uint8_t* Y, int64_t n, int64_t nbytes, 
     }
     if (rc == BBH_OK) rc = o1.finish(s);
     if (rc == BBH_OK) rc = o2.finish(s);
-    hipError_t e = hipStreamSynchronize(s);
-    bb::dev_free(scratch);
-    if (rc == BBH_OK && e != hipSuccess) rc = bb::fail(BBH_ERR_HIP, "most_dissimilar: %s", hipGetErrorString(e));
+    if (rc == BBH_OK) rc = tmp.sync("most_dissimilar");
     if (rc == BBH_OK) {
         *idx1 = hidx[0];
         *idx2 = hidx[1];

@@ -421,21 +421,6 @@ int seg_cu_count() {
     return n;
 }
 
-struct SegScratch {  // device blocks of one call, returned to the cache on every exit path
-    std::vector<void*> blocks;
-    template <typename T>
-    hipError_t get(T** p, size_t bytes) {
-        void* v = nullptr;
-        hipError_t e = bb::dev_alloc(&v, bytes ? bytes : 4);
-        if (e == hipSuccess) blocks.push_back(v);
-        *p = (T*)v;
-        return e;
-    }
-    ~SegScratch() {
-        for (void* b : blocks) bb::dev_free(b);
-    }
-};
-
 int bit_length(int64_t v) {
     int n = 0;
     while (v > 0) {
@@ -502,7 +487,7 @@ extern "C" int bbh_compl_isim_segments(const uint8_t* rows, int64_t n_rows, int6
                 return bb::fail(BBH_ERR_INVALID, "compl_isim_segments: members[%lld] = %lld is not a row", (long long)i,
                                 (long long)members[i]);
     }
-    SegScratch tmp;
+    bb::DevScope tmp(s);
     BB_TRY(d_mem.init(members, (size_t)total * 8, s));
     if (mem_dev) {
         int* flag = nullptr;
@@ -514,7 +499,7 @@ extern "C" int bbh_compl_isim_segments(const uint8_t* rows, int64_t n_rows, int6
         BB_HIP(hipGetLastError());
         int bad = 0;
         BB_HIP(hipMemcpyAsync(&bad, flag, 4, hipMemcpyDeviceToHost, s));
-        BB_HIP(hipStreamSynchronize(s));
+        BB_TRY(tmp.sync());
         if (bad) return bb::fail(BBH_ERR_INVALID, "compl_isim_segments: an entry of members is not a row");
     }
     BB_TRY(d_rows.init(rows, (size_t)((n_rows - 1) * row_stride + nbytes), s));
@@ -590,7 +575,5 @@ extern "C" int bbh_compl_isim_segments(const uint8_t* rows, int64_t n_rows, int6
     }
     BB_TRY(o_compl.finish(s));
     BB_TRY(o_med.finish(s));
-    // (staging and scratch blocks go back to the cache when this returns: the stream must be done with them)
-    BB_HIP(hipStreamSynchronize(s));
-    return BBH_OK;
+    return tmp.sync();
 }

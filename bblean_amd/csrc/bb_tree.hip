@@ -2488,17 +2488,22 @@ static const TreeEnv& tree_env() {
 }
 
 // `used_elems`: the prefix of the old pool that holds live data (only that much is carried over)
-template <typename T>
-int grow_pool(T*& p, size_t used_elems, size_t new_elems) {
+int grow_pool(void** p, size_t elem_bytes, size_t used_elems, size_t new_elems) {
     // (allocate, copy, free: the old pool and the new one exist side by side for the length of the copy.  Growing in place
     // with the virtual-memory calls - hipMemAddressReserve / hipMemCreate / hipMemMap - was tried in round 4: mappings of a
     // few KB behaved, a 2.2 GB chunk with a 1 GB chunk mapped behind it took a memory access fault on the first touch
     // (tools/probe/vmm_probe.cpp, profiles/r04/vmm_probe.txt), so the pools stay plain allocations.)
-    T* np_ = nullptr;
-    BB_HIP(bb::dev_alloc(&np_, new_elems * sizeof(T) + 64));  // slack: cf_load_raw over-reads 8 bytes
-    if (p && used_elems) BB_HIP(hipMemcpy(np_, p, used_elems * sizeof(T), hipMemcpyDeviceToDevice));
-    if (p) bb::dev_free(p);
-    p = np_;
+    void* np_ = nullptr;
+    BB_HIP(bb::dev_alloc(&np_, new_elems * elem_bytes + 64));  // slack: cf_load_raw over-reads 8 bytes
+    if (*p && used_elems) {
+        const hipError_t e = hipMemcpy(np_, *p, used_elems * elem_bytes, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {  // (the new block is this function's until the copy has succeeded)
+            bb::dev_free(np_);
+            BB_HIP(e);
+        }
+    }
+    bb::dev_free(*p);
+    *p = np_;
     return BBH_OK;
 }
 
@@ -2549,50 +2554,75 @@ static void note_peak(bbh_tree* t, size_t extra) { t->peak_bytes = std::max(t->p
 // wherever a node starts, whatever its capacity (rows beyond its length are masked).
 static size_t pool_rows(const TreeDev& h, size_t blocks) { return blocks * NG + (size_t)h.bf + 1 + NG; }
 
-// new node pools of `nc` blocks; the first `keep` blocks of the old ones are carried over (`keep` == 0: nothing).  Headers
-// beyond `keep` are zeroed: a header with capacity 0 starts no node, which is how the compaction tells a node's first
-// block from its other blocks and from blocks that were given up (thaw_node).
-static int realloc_node_pools(bbh_tree* t, size_t keep, size_t nc, TreeDev* fresh_only = nullptr) {
-    TreeDev& h = t->h;
-    const size_t rb = (size_t)h.RB;
-    TreeDev n = h;
-    n.node_cent = nullptr; n.node_card = nullptr; n.node_link = nullptr; n.node_rm = nullptr; n.node_hdr = nullptr;
-    const size_t nr = pool_rows(h, nc);
-    hipError_t e = bb::dev_alloc(&n.node_cent, nr * rb + 64);
-    if (e == hipSuccess) e = bb::dev_alloc(&n.node_card, nr * 4 + 64);
-    if (e == hipSuccess) e = bb::dev_alloc(&n.node_link, nr * 4 + 64);
-    if (e == hipSuccess) e = bb::dev_alloc(&n.node_rm, nr * sizeof(RowMeta) + 64);
-    if (e == hipSuccess) e = bb::dev_alloc(&n.node_hdr, (nc + 1) * sizeof(NodeHdr));
+// The five node pools as one value (host side; TreeDev's node_* members): allocated all or nothing, owned until they are given to a tree.
+struct NodePools {
+    uint8_t* cent = nullptr;
+    uint32_t* card = nullptr;
+    uint32_t* link = nullptr;
+    RowMeta* rm = nullptr;
+    NodeHdr* hdr = nullptr;
+    NodePools() = default;
+    NodePools(const NodePools&) = delete;
+    NodePools& operator=(const NodePools&) = delete;
+    hipError_t alloc(const TreeDev& h, size_t blocks) {  // (all or nothing)
+        const size_t nr = pool_rows(h, blocks);
+        hipError_t e = bb::dev_alloc(&cent, nr * (size_t)h.RB + 64);
+        if (e == hipSuccess) e = bb::dev_alloc(&card, nr * 4 + 64);
+        if (e == hipSuccess) e = bb::dev_alloc(&link, nr * 4 + 64);
+        if (e == hipSuccess) e = bb::dev_alloc(&rm, nr * sizeof(RowMeta) + 64);
+        if (e == hipSuccess) e = bb::dev_alloc(&hdr, (blocks + 1) * sizeof(NodeHdr));
+        if (e != hipSuccess) free();
+        return e;
+    }
+    void free() {
+        bb::dev_free(cent); bb::dev_free(card); bb::dev_free(link); bb::dev_free(rm); bb::dev_free(hdr);
+        cent = nullptr; card = nullptr; link = nullptr; rm = nullptr; hdr = nullptr;
+    }
+    void take(TreeDev& h) {  // the tree's pools move out (this value holds none)
+        cent = h.node_cent; card = h.node_card; link = h.node_link; rm = h.node_rm; hdr = h.node_hdr;
+        h.node_cent = nullptr; h.node_card = nullptr; h.node_link = nullptr; h.node_rm = nullptr; h.node_hdr = nullptr;
+    }
+    void give(TreeDev& h) {  // ... and in: the pointers, nothing else (cap_nodes is the caller's)
+        h.node_cent = cent; h.node_card = card; h.node_link = link; h.node_rm = rm; h.node_hdr = hdr;
+        cent = nullptr; card = nullptr; link = nullptr; rm = nullptr; hdr = nullptr;
+    }
+    ~NodePools() { free(); }
+};
+
+// new node pools of `nc` blocks for `t`, not yet its own
+static int alloc_node_pools(bbh_tree* t, size_t nc, NodePools& n) {
+    const TreeDev& h = t->h;
+    const hipError_t e = n.alloc(h, nc);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        void* ptrs[] = {n.node_cent, n.node_card, n.node_link, n.node_rm, n.node_hdr};
-        for (void* q : ptrs)
-            if (q) bb::dev_free(q);
         return bb::fail(BBH_ERR_CAPACITY, "node pools of %zu blocks (%.2f GB) could not be allocated: %s", nc, (double)nc * (double)block_bytes(h) / 1e9,
                         hipGetErrorString(e));
     }
     note_peak(t, nc * block_bytes(h));
-    if (fresh_only) {  // (the compaction fills the new pools itself and swaps them in)
-        BB_HIP(hipMemset(n.node_hdr, 0, (nc + 1) * sizeof(NodeHdr)));
-        *fresh_only = n;
-        return BBH_OK;
-    }
+    return BBH_OK;
+}
+
+// new node pools of `nc` blocks; the first `keep` blocks of the old ones are carried over (`keep` == 0: nothing).  Headers
+// beyond `keep` are zeroed: a header with capacity 0 starts no node, which is how the compaction tells a node's first
+// block from its other blocks and from blocks that were given up (thaw_node).
+static int realloc_node_pools(bbh_tree* t, size_t keep, size_t nc) {
+    TreeDev& h = t->h;
+    NodePools n;  // (owned here until the carry-over is done: an error below gives them back)
+    BB_TRY(alloc_node_pools(t, nc, n));
     // (the memset first: whatever blocking copy follows on the null stream - the carried-over part here, the root header of
     // a tree without rows in the callers - returns when both are done; a memset left in flight could land on a header a
     // kernel on another stream has written since)
-    BB_HIP(hipMemset(n.node_hdr + keep, 0, (nc + 1 - keep) * sizeof(NodeHdr)));
+    BB_HIP(hipMemset(n.hdr + keep, 0, (nc + 1 - keep) * sizeof(NodeHdr)));
     if (keep) {
         const size_t kr = keep * NG;
-        BB_HIP(hipMemcpy(n.node_cent, h.node_cent, kr * rb, hipMemcpyDeviceToDevice));
-        BB_HIP(hipMemcpy(n.node_card, h.node_card, kr * 4, hipMemcpyDeviceToDevice));
-        BB_HIP(hipMemcpy(n.node_link, h.node_link, kr * 4, hipMemcpyDeviceToDevice));
-        BB_HIP(hipMemcpy(n.node_rm, h.node_rm, kr * sizeof(RowMeta), hipMemcpyDeviceToDevice));
-        BB_HIP(hipMemcpy(n.node_hdr, h.node_hdr, keep * sizeof(NodeHdr), hipMemcpyDeviceToDevice));
+        BB_HIP(hipMemcpy(n.cent, h.node_cent, kr * (size_t)h.RB, hipMemcpyDeviceToDevice));
+        BB_HIP(hipMemcpy(n.card, h.node_card, kr * 4, hipMemcpyDeviceToDevice));
+        BB_HIP(hipMemcpy(n.link, h.node_link, kr * 4, hipMemcpyDeviceToDevice));
+        BB_HIP(hipMemcpy(n.rm, h.node_rm, kr * sizeof(RowMeta), hipMemcpyDeviceToDevice));
+        BB_HIP(hipMemcpy(n.hdr, h.node_hdr, keep * sizeof(NodeHdr), hipMemcpyDeviceToDevice));
     }
-    void* old[] = {h.node_cent, h.node_card, h.node_link, h.node_rm, h.node_hdr};
-    for (void* q : old)
-        if (q) bb::dev_free(q);
-    h.node_cent = n.node_cent; h.node_card = n.node_card; h.node_link = n.node_link; h.node_rm = n.node_rm; h.node_hdr = n.node_hdr;
+    NodePools().take(h);  // (the old pools go after the carry-over)
+    n.give(h);
     h.cap_nodes = (uint32_t)nc;
     return BBH_OK;
 }
@@ -2616,86 +2646,80 @@ int gc_nodes(bbh_tree* t, uint64_t extra, int seal) {
     TreeDev& h = t->h;
     const uint32_t used = std::min(h.cap_nodes, h.ctr[C_NODES]);
     const uint32_t rows = (uint32_t)h.bf + 1;
+    NodePools fresh;            // (declared first: freed after the scope below has synchronised)
+    bb::DevScope tmp(nullptr);  // (the null stream and blocking copies throughout)
     uint32_t *d_sz = nullptr, *d_id = nullptr;
     unsigned long long* d_cnt = nullptr;
     void* d_tmp = nullptr;
-    int rc = BBH_OK;
-    TreeDev fresh{};
-    bool have_fresh = false;
-    auto body = [&]() -> int {
-        BB_HIP(bb::dev_alloc(&d_sz, ((size_t)used + 1) * 4));
-        BB_HIP(bb::dev_alloc(&d_id, ((size_t)used + 1) * 4));
-        BB_HIP(bb::dev_alloc(&d_cnt, 16));
-        BB_HIP(hipMemset(d_cnt, 0, 16));
-        BB_HIP(hipMemset(d_sz + used, 0, 4));
-        hipLaunchKernelGGL(k_gc_size, dim3((used + 255) / 256), dim3(256), 0, 0, (const NodeHdr*)h.node_hdr, used, rows, h.ctr[C_ROOT], seal, d_sz, d_cnt);
-        BB_HIP(hipGetLastError());
-        size_t tmp_bytes = 0;
-        BB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_sz, d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
-        BB_HIP(bb::dev_alloc(&d_tmp, tmp_bytes + 16));
-        BB_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_sz, d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
-        uint32_t total = 0, new_root = 0, new_first = NONE;
-        unsigned long long cnt[2] = {0, 0};
-        BB_HIP(hipMemcpy(&total, d_id + used, 4, hipMemcpyDeviceToHost));
-        BB_HIP(hipMemcpy(&new_root, d_id + h.ctr[C_ROOT], 4, hipMemcpyDeviceToHost));
-        if (h.ctr[C_FIRST_LEAF] != NONE && h.ctr[C_FIRST_LEAF] < used) BB_HIP(hipMemcpy(&new_first, d_id + h.ctr[C_FIRST_LEAF], 4, hipMemcpyDeviceToHost));
-        BB_HIP(hipMemcpy(cnt, d_cnt, 16, hipMemcpyDeviceToHost));
-        // what the new pools hold: everything live, and room for `extra` blocks or a quarter more - within what the device has
-        // free right now (the old pools stay until the move is done)
-        const uint64_t floor_b = (uint64_t)total + (2 * (uint64_t)h.ctr[C_DEPTH] + 8) * node_blocks(rows);
-        uint64_t want = (uint64_t)total + std::max<uint64_t>(extra, tiny_pools() ? 0 : (uint64_t)total / 4);
-        want = std::max(want, floor_b);
-        size_t free_b = 0;
-        // (what is free AFTER the caches - this library's and, through the memory-pressure callback, the host side's - have been
-        // emptied, if the first answer is short of `want`: ADVICE r5)
-        if (bb::dev_free_bytes((size_t)((double)want * (double)block_bytes(h) / 0.92) + 1, &free_b) == hipSuccess) {
-            const uint64_t room = (uint64_t)((double)free_b * 0.92) / block_bytes(h);
-            if (want > room) {
-                // (near the end of the device's memory the pool takes what is left - but not in steps so small that every few
-                // thousand elements copy all of it again: ADVICE r4)
-                const uint64_t least = std::max<uint64_t>(floor_b, (uint64_t)total + std::min<uint64_t>(extra, (uint64_t)total / 32 + 1024));
-                if (room < least)
-                    return bb::fail(BBH_ERR_CAPACITY, "out of device memory: the node pools hold %.2f GB after compaction and %.2f GB are free", (double)total * (double)block_bytes(h) / 1e9, (double)free_b / 1e9);
-                want = room;
-            }
-        } else {
-            (void)hipGetLastError();
+    BB_HIP(tmp.get(&d_sz, ((size_t)used + 1) * 4));
+    BB_HIP(tmp.get(&d_id, ((size_t)used + 1) * 4));
+    BB_HIP(tmp.get(&d_cnt, 16));
+    BB_HIP(hipMemset(d_cnt, 0, 16));
+    BB_HIP(hipMemset(d_sz + used, 0, 4));
+    hipLaunchKernelGGL(k_gc_size, dim3((used + 255) / 256), dim3(256), 0, 0, (const NodeHdr*)h.node_hdr, used, rows, h.ctr[C_ROOT], seal, d_sz, d_cnt);
+    BB_HIP(hipGetLastError());
+    size_t tmp_bytes = 0;
+    BB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_sz, d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
+    BB_HIP(tmp.get(&d_tmp, tmp_bytes + 16));
+    BB_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_sz, d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
+    uint32_t total = 0, new_root = 0, new_first = NONE;
+    unsigned long long cnt[2] = {0, 0};
+    BB_HIP(hipMemcpy(&total, d_id + used, 4, hipMemcpyDeviceToHost));
+    BB_HIP(hipMemcpy(&new_root, d_id + h.ctr[C_ROOT], 4, hipMemcpyDeviceToHost));
+    if (h.ctr[C_FIRST_LEAF] != NONE && h.ctr[C_FIRST_LEAF] < used) BB_HIP(hipMemcpy(&new_first, d_id + h.ctr[C_FIRST_LEAF], 4, hipMemcpyDeviceToHost));
+    BB_HIP(hipMemcpy(cnt, d_cnt, 16, hipMemcpyDeviceToHost));
+    // what the new pools hold: everything live, and room for `extra` blocks or a quarter more - within what the device has
+    // free right now (the old pools stay until the move is done)
+    const uint64_t floor_b = (uint64_t)total + (2 * (uint64_t)h.ctr[C_DEPTH] + 8) * node_blocks(rows);
+    uint64_t want = (uint64_t)total + std::max<uint64_t>(extra, tiny_pools() ? 0 : (uint64_t)total / 4);
+    want = std::max(want, floor_b);
+    size_t free_b = 0;
+    // (what is free AFTER the caches - this library's and, through the memory-pressure callback, the host side's - have been
+    // emptied, if the first answer is short of `want`: ADVICE r5)
+    if (bb::dev_free_bytes((size_t)((double)want * (double)block_bytes(h) / 0.92) + 1, &free_b) == hipSuccess) {
+        const uint64_t room = (uint64_t)((double)free_b * 0.92) / block_bytes(h);
+        if (want > room) {
+            // (near the end of the device's memory the pool takes what is left - but not in steps so small that every few
+            // thousand elements copy all of it again: ADVICE r4)
+            const uint64_t least = std::max<uint64_t>(floor_b, (uint64_t)total + std::min<uint64_t>(extra, (uint64_t)total / 32 + 1024));
+            if (room < least)
+                return bb::fail(BBH_ERR_CAPACITY, "out of device memory: the node pools hold %.2f GB after compaction and %.2f GB are free", (double)total * (double)block_bytes(h) / 1e9, (double)free_b / 1e9);
+            want = room;
         }
-        if (want > 0x3FFFFFFFull) want = 0x3FFFFFFFull;
-        if (want < floor_b) return bb::fail(BBH_ERR_CAPACITY, "node pool limit of 2^30 blocks reached");
-        BB_TRY(realloc_node_pools(t, 0, (size_t)want, &fresh));
-        have_fresh = true;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)used + 3) / 4, 1u << 16);
-        hipLaunchKernelGGL(k_gc_move, dim3(std::max(grid, 1u)), dim3(256), 0, 0, h, fresh, used, rows, (const uint32_t*)d_sz, (const uint32_t*)d_id);
-        BB_HIP(hipGetLastError());
-        BB_HIP(hipDeviceSynchronize());
-        void* old[] = {h.node_cent, h.node_card, h.node_link, h.node_rm, h.node_hdr};
-        for (void* q : old)
-            if (q) bb::dev_free(q);
-        h.node_cent = fresh.node_cent; h.node_card = fresh.node_card; h.node_link = fresh.node_link; h.node_rm = fresh.node_rm; h.node_hdr = fresh.node_hdr;
-        have_fresh = false;
-        h.cap_nodes = (uint32_t)want;
-        t->gc_runs += 1; t->gc_full = cnt[0]; t->gc_sealed = cnt[1]; t->gc_before = used; t->gc_after = total;
-        h.ctr[C_NODES] = total;
-        h.ctr[C_ROOT] = new_root;
-        h.ctr[C_FIRST_LEAF] = new_first;
-        t->chain_valid = false;
-        if (tree_env().gc_log)
-            fprintf(stderr, "[bbhip gc] #%llu blocks %u -> %u (%.3f -> %.3f GB), nodes full %llu sealed %llu, new pool %.3f GB\n", (unsigned long long)t->gc_runs, used, total,
-                    (double)used * (double)block_bytes(h) / 1e9, (double)total * (double)block_bytes(h) / 1e9, cnt[0], cnt[1], (double)want * (double)block_bytes(h) / 1e9);
-        return BBH_OK;
-    };
-    rc = body();
-    if (have_fresh) {
-        void* ptrs[] = {fresh.node_cent, fresh.node_card, fresh.node_link, fresh.node_rm, fresh.node_hdr};
-        for (void* q : ptrs)
-            if (q) bb::dev_free(q);
+    } else {
+        (void)hipGetLastError();
     }
-    if (d_sz) bb::dev_free(d_sz);
-    if (d_id) bb::dev_free(d_id);
-    if (d_cnt) bb::dev_free(d_cnt);
-    if (d_tmp) bb::dev_free(d_tmp);
-    return rc;
+    if (want > 0x3FFFFFFFull) want = 0x3FFFFFFFull;
+    if (want < floor_b) return bb::fail(BBH_ERR_CAPACITY, "node pool limit of 2^30 blocks reached");
+    BB_TRY(alloc_node_pools(t, (size_t)want, fresh));
+    BB_HIP(hipMemset(fresh.hdr, 0, ((size_t)want + 1) * sizeof(NodeHdr)));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)used + 3) / 4, 1u << 16);
+    TreeDev moved = h;  // the tree as the kernel fills it: the new pools are lent to this copy for the launch
+    fresh.give(moved);
+    hipLaunchKernelGGL(k_gc_move, dim3(std::max(grid, 1u)), dim3(256), 0, 0, h, moved, used, rows, (const uint32_t*)d_sz, (const uint32_t*)d_id);
+    fresh.take(moved);
+    BB_HIP(hipGetLastError());
+    BB_HIP(hipDeviceSynchronize());
+    NodePools().take(h);  // (the old pools go only now: the move has been synchronised)
+    fresh.give(h);
+    h.cap_nodes = (uint32_t)want;
+    t->gc_runs += 1; t->gc_full = cnt[0]; t->gc_sealed = cnt[1]; t->gc_before = used; t->gc_after = total;
+    h.ctr[C_NODES] = total;
+    h.ctr[C_ROOT] = new_root;
+    h.ctr[C_FIRST_LEAF] = new_first;
+    t->chain_valid = false;
+    if (tree_env().gc_log)
+        fprintf(stderr, "[bbhip gc] #%llu blocks %u -> %u (%.3f -> %.3f GB), nodes full %llu sealed %llu, new pool %.3f GB\n", (unsigned long long)t->gc_runs, used, total,
+                (double)used * (double)block_bytes(h) / 1e9, (double)total * (double)block_bytes(h) / 1e9, cnt[0], cnt[1], (double)want * (double)block_bytes(h) / 1e9);
+    return BBH_OK;
+}
+
+// the header of an empty leaf root into block 0 (a blocking copy on the null stream)
+static int write_empty_root(const TreeDev& h) {
+    NodeHdr root;
+    root.len = 0; root.leaf = hw_make(1u, (uint32_t)h.bf + 1); root.prev = NONE; root.next = NONE;
+    BB_HIP(hipMemcpy(h.node_hdr, &root, sizeof(root), hipMemcpyHostToDevice));
+    return BBH_OK;
 }
 
 // `want`: blocks the node pools should hold.  Small pools grow by copying; pools beyond BBHIP_GC_MIN_MB are compacted on the
@@ -2714,11 +2738,7 @@ int grow_nodes(bbh_tree* t, uint32_t want, uint64_t gc_extra = 0) {  // (gc_extr
         want = fit_to_memory(grow_target(h.cap_nodes, want), std::max(floor_elems, h.cap_nodes + 1), h.cap_nodes, block_bytes(h));
     }
     BB_TRY(realloc_node_pools(t, pristine ? 0 : used, want));
-    if (pristine) {
-        NodeHdr root;
-        root.len = 0; root.leaf = hw_make(1u, (uint32_t)h.bf + 1); root.prev = NONE; root.next = NONE;
-        BB_HIP(hipMemcpy(h.node_hdr, &root, sizeof(root), hipMemcpyHostToDevice));
-    }
+    if (pristine) BB_TRY(write_empty_root(h));
     return BBH_OK;
 }
 
@@ -2729,28 +2749,24 @@ int grow_cf(bbh_tree* t, int tier, uint32_t want) {
     // looked at.  A multiround round creates hundreds of trees and grows three pools of each of them right away: three
     // blocking 2 KB copies per tree were a third of bench.py's `concurrent_shards` wall time)
     const bool pristine = h.ctr[C_IDS] == 0 && h.stats[3] == 0 && h.ctr[C_N16] == 0 && h.ctr[C_N32] == 0 && h.ctr[C_N8] <= 1;
-    if (tier == 0 && want > h.cap8) {
-        want = fit_to_memory(grow_target(h.cap8, want, F), std::max<uint32_t>(clamp30((uint64_t)h.ctr[C_N8] + 2 * (uint64_t)h.ctr[C_DEPTH] + 64), h.cap8 + 1), h.cap8, F * 1);
-        BB_TRY(grow_pool(h.cf8, pristine ? 0 : (size_t)std::min(h.cap8, h.ctr[C_N8]) * F, (size_t)want * F));
-        h.cap8 = want;
-    } else if (tier == 1 && want > h.cap16) {
-        want = fit_to_memory(grow_target(h.cap16, want, F * 2), std::max<uint32_t>(clamp30((uint64_t)h.ctr[C_N16] + 2 * (uint64_t)h.ctr[C_DEPTH] + 64), h.cap16 + 1), h.cap16, F * 2);
-        BB_TRY(grow_pool(h.cf16, (size_t)std::min(h.cap16, h.ctr[C_N16]) * F, (size_t)want * F));
-        h.cap16 = want;
-    } else if (tier == 2 && want > h.cap32) {
-        want = fit_to_memory(grow_target(h.cap32, want, F * 4), std::max<uint32_t>(clamp30((uint64_t)h.ctr[C_N32] + 2 * (uint64_t)h.ctr[C_DEPTH] + 64), h.cap32 + 1), h.cap32, F * 4);
-        BB_TRY(grow_pool(h.cf32, (size_t)std::min(h.cap32, h.ctr[C_N32]) * F, (size_t)want * F));
-        h.cap32 = want;
-    }
+    // pool, capacity, counter of the slots in use, bytes per feature (grow_target / fit_to_memory reckon in bytes per slot,
+    // grow_pool in elements of that many bytes)
+    const struct { void** pool; uint32_t* cap; int ctr; size_t bytes; } tiers[3] = {
+        {(void**)&h.cf8, &h.cap8, C_N8, 1}, {(void**)&h.cf16, &h.cap16, C_N16, 2}, {(void**)&h.cf32, &h.cap32, C_N32, 4}};
+    if (tier < 0 || tier > 2 || want <= *tiers[tier].cap) return BBH_OK;
+    const auto& T = tiers[tier];
+    const uint32_t cap = *T.cap, n = h.ctr[T.ctr];
+    want = fit_to_memory(grow_target(cap, want, F * T.bytes), std::max<uint32_t>(clamp30((uint64_t)n + 2 * (uint64_t)h.ctr[C_DEPTH] + 64), cap + 1), cap, F * T.bytes);
+    BB_TRY(grow_pool(T.pool, T.bytes, pristine && tier == 0 ? 0 : (size_t)std::min(cap, n) * F, (size_t)want * F));
+    *T.cap = want;
     return BBH_OK;
 }
 
 void free_pools(bbh_tree* t) {
     TreeDev& h = t->h;
-    void* ptrs[] = {h.node_cent, h.node_card, h.node_link, h.node_rm, h.node_hdr, h.scratch_cent, h.cf8, h.cf16, h.cf32};
-    for (void* p : ptrs)
-        if (p) bb::dev_free(p);
-    h.node_cent = nullptr; h.node_card = nullptr; h.node_link = nullptr; h.node_rm = nullptr; h.node_hdr = nullptr;
+    NodePools().take(h);
+    void* ptrs[] = {h.scratch_cent, h.cf8, h.cf16, h.cf32};
+    for (void* p : ptrs) bb::dev_free(p);
     h.scratch_cent = nullptr; h.cf8 = nullptr; h.cf16 = nullptr; h.cf32 = nullptr;
     h.cap_nodes = h.cap8 = h.cap16 = h.cap32 = 0;
 }
@@ -2765,10 +2781,8 @@ int init_empty(bbh_tree* t) {
     // minimal pools here and regrowing all of them in the first fit was most of what such a tree cost the host.
     t->lazy_pools = h.cap_nodes == 0;
     if (!t->lazy_pools) {  // a reset tree keeps its pools: no header of the old tree survives
-        NodeHdr root;
-        root.len = 0; root.leaf = hw_make(1u, (uint32_t)h.bf + 1); root.prev = NONE; root.next = NONE;
         BB_HIP(hipMemset(h.node_hdr, 0, ((size_t)h.cap_nodes + 1) * sizeof(NodeHdr)));
-        BB_HIP(hipMemcpy(h.node_hdr, &root, sizeof(root), hipMemcpyHostToDevice));
+        BB_TRY(write_empty_root(h));
     }
     h.ctr[C_NODES] = nblk;
     h.ctr[C_N8] = 1;  // (slot 0 of the uint8 pool is SLOT_LAZY8: never a BitFeature's)
@@ -3095,9 +3109,10 @@ int grow_after_stop(bbh_tree* t, const Job& j, const TreeDev& back, int64_t left
 int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
     if (jobs.empty()) return BBH_OK;
     const TreeEnv& env = tree_env();
+    bb::DevScope tmp(s);
     TreeDev* darr = nullptr;
     const bool single = jobs.size() == 1;
-    if (!single) BB_HIP(bb::dev_alloc(&darr, jobs.size() * sizeof(TreeDev)));
+    if (!single) BB_HIP(tmp.get(&darr, jobs.size() * sizeof(TreeDev)));
     std::vector<TreeDev> harr(jobs.size());
     std::vector<size_t> active;
     int rc = BBH_OK;
@@ -3247,8 +3262,9 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
 
         // ---- 7. read back, 8. the pipelined kernel's run-end audit, 9. the launch log
         if (e == hipSuccess) e = hipMemcpyAsync(harr.data(), dptr, active.size() * sizeof(TreeDev), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { rc = bb::fail(BBH_ERR_HIP, "tree_insert: %s", hipGetErrorString(e)); break; }
+        rc = tmp.sync("tree_insert");
+        if (rc != BBH_OK) break;
         if (engine == Engine::Pipe && harr[0].audit) {
             unsigned int au = 0;
             (void)hipMemcpyFromSymbol(&au, HIP_SYMBOL(g_pipe_audit), sizeof(au));
@@ -3325,7 +3341,6 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
             }
         }
     }
-    if (darr) (void)bb::dev_free(darr);
     return rc;
 }
 
@@ -3348,25 +3363,20 @@ int build_chain(bbh_tree* t) {
     struct LeafHdr { uint32_t id, len, next; };
     std::vector<LeafHdr> lh;
     if (nn) {
-        uint32_t* d_count = nullptr;
-        BB_HIP(bb::dev_alloc(&d_count, 64));
+        bb::DevScope tmp(nullptr);
+        uint32_t *d_count = nullptr, *d_out = nullptr;
+        BB_HIP(tmp.get(&d_count, 64));
         BB_HIP(hipMemset(d_count, 0, 4));
         hipLaunchKernelGGL(k_leaf_headers, dim3((nn + 255) / 256), dim3(256), 0, 0, (const NodeHdr*)h.node_hdr, nn, d_count, (uint32_t*)nullptr, 0u);
         uint32_t count = 0;
-        hipError_t e = hipMemcpy(&count, d_count, 4, hipMemcpyDeviceToHost);
-        uint32_t* d_out = nullptr;
-        if (e == hipSuccess && count) e = bb::dev_alloc(&d_out, (size_t)count * 12);
-        if (e == hipSuccess && count) {
-            e = hipMemset(d_count, 0, 4);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_leaf_headers, dim3((nn + 255) / 256), dim3(256), 0, 0, (const NodeHdr*)h.node_hdr, nn, d_count, d_out, count);
-                lh.resize(count);
-                e = hipMemcpy(lh.data(), d_out, (size_t)count * 12, hipMemcpyDeviceToHost);
-            }
+        BB_HIP(hipMemcpy(&count, d_count, 4, hipMemcpyDeviceToHost));
+        if (count) {
+            BB_HIP(tmp.get(&d_out, (size_t)count * 12));
+            BB_HIP(hipMemset(d_count, 0, 4));
+            hipLaunchKernelGGL(k_leaf_headers, dim3((nn + 255) / 256), dim3(256), 0, 0, (const NodeHdr*)h.node_hdr, nn, d_count, d_out, count);
+            lh.resize(count);
+            BB_HIP(hipMemcpy(lh.data(), d_out, (size_t)count * 12, hipMemcpyDeviceToHost));
         }
-        if (d_out) (void)bb::dev_free(d_out);
-        (void)bb::dev_free(d_count);
-        BB_HIP(e);
         std::sort(lh.begin(), lh.end(), [](const LeafHdr& a, const LeafHdr& b) { return a.id < b.id; });
     }
     t->chain_nodes.clear();
@@ -3592,6 +3602,7 @@ static int insert_u8_buffers(bbh_tree* t, const uint8_t* d, int64_t m, const uin
     const int64_t kMinRun = 1024;
     const size_t row_bytes = (size_t)t->h.F + 1;
     const int nbytes = t->h.nbytes;
+    bb::DevScope tmp(s);  // (no sync() here: the destructor synchronises before `packed` goes, as this function always did)
     uint8_t* packed = nullptr;
     int rc = BBH_OK;
     for (int64_t lo = 0; lo < m && rc == BBH_OK;) {
@@ -3600,7 +3611,7 @@ static int insert_u8_buffers(bbh_tree* t, const uint8_t* d, int64_t m, const uin
         while (hi < m && n_col[hi] == 1) ++hi;
         if (hi - lo >= kMinRun) {
             if (!packed) {
-                hipError_t e = bb::dev_alloc(&packed, (size_t)m * nbytes);
+                hipError_t e = tmp.get(&packed, (size_t)m * nbytes);
                 if (e != hipSuccess) return bb::fail(BBH_ERR_HIP, "dev_alloc: %s", hipGetErrorString(e));
             }
             // (at most 2^22 rows per launch: the global size of a launch is a 32-bit number)
@@ -3631,10 +3642,6 @@ static int insert_u8_buffers(bbh_tree* t, const uint8_t* d, int64_t m, const uin
         rc = run_insert(t, nullptr, 0, d + (size_t)lo * row_bytes, 1, hi - lo, out ? out + lo : nullptr, s);
         lo = hi;
     }
-    if (packed) {
-        (void)hipStreamSynchronize(s);
-        bb::dev_free(packed);
-    }
     return rc;
 }
 
@@ -3657,14 +3664,15 @@ extern "C" int bbh_tree_fit_buffers(bbh_tree* t, const void* bufs, int32_t width
             // the n_samples column: gathered on the device, one contiguous copy (a 1-byte-wide hipMemcpy2D over
             // 360 k rows took half a second)
             std::vector<uint8_t> n_col((size_t)k);
-            uint8_t* col = nullptr;
-            BB_HIP(bb::dev_alloc(&col, (size_t)k));
-            hipLaunchKernelGGL(k_gather_n_col, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, (const uint8_t*)bufs, (long long)k,
-                               t->h.F, col);
-            hipError_t ce = hipMemcpyAsync(n_col.data(), col, (size_t)k, hipMemcpyDeviceToHost, s);
-            if (ce == hipSuccess) ce = hipStreamSynchronize(s);
-            (void)bb::dev_free(col);
-            BB_HIP(ce);
+            {
+                bb::DevScope tmp(s);
+                uint8_t* col = nullptr;
+                BB_HIP(tmp.get(&col, (size_t)k));
+                hipLaunchKernelGGL(k_gather_n_col, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, (const uint8_t*)bufs, (long long)k,
+                                   t->h.F, col);
+                BB_HIP(hipMemcpyAsync(n_col.data(), col, (size_t)k, hipMemcpyDeviceToHost, s));
+                BB_TRY(tmp.sync());
+            }
             BB_TRY(insert_u8_buffers(t, (const uint8_t*)bufs, k, n_col.data(), (uint32_t*)o.dev, s));
         } else {
             BB_TRY(run_insert(t, nullptr, 0, (const uint8_t*)bufs, width, k, (uint32_t*)o.dev, s));
@@ -3831,17 +3839,14 @@ static int gather_positions(bbh_tree* t, const int64_t* positions, int64_t m, in
         nodes[(size_t)i] = t->chain_nodes[(size_t)positions[i]];
         rows[(size_t)i] = t->chain_rows[(size_t)positions[i]];
     }
+    bb::DevScope tmp(nullptr);  // (gather works on the null stream)
     uint32_t *dn = nullptr, *dr = nullptr;
-    BB_HIP(bb::dev_alloc(&dn, (size_t)m * 4));
-    BB_HIP(bb::dev_alloc(&dr, (size_t)m * 4));
-    int rc = BBH_OK;
+    BB_HIP(tmp.get(&dn, (size_t)m * 4));
+    BB_HIP(tmp.get(&dr, (size_t)m * 4));
     if (hipMemcpy(dn, nodes.data(), (size_t)m * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(dr, rows.data(), (size_t)m * 4, hipMemcpyHostToDevice) != hipSuccess)
-        rc = bb::fail(BBH_ERR_HIP, "gather: H2D failed");
-    if (rc == BBH_OK) rc = gather(t, dn, dr, m, width, bufs, 0, cents, nullptr, nullptr);
-    (void)bb::dev_free(dn);
-    (void)bb::dev_free(dr);
-    return rc;
+        return bb::fail(BBH_ERR_HIP, "gather: H2D failed");
+    return gather(t, dn, dr, m, width, bufs, 0, cents, nullptr, nullptr);
 }
 
 extern "C" int bbh_tree_gather_buffers(bbh_tree* t, const int64_t* positions, int64_t m, int32_t width, void* out) {

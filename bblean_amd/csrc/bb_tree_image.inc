@@ -320,20 +320,6 @@ int img_check(int fd, uint64_t base, ImgHeader* out) {
     return BBH_OK;
 }
 
-// device and pinned buffers of one save / load call
-struct ImgBuffers {
-    uint32_t *d_sz = nullptr, *d_id = nullptr;
-    void* d_tmp = nullptr;
-    uint8_t *d_stage = nullptr, *pin = nullptr;
-    ~ImgBuffers() {
-        if (d_sz) bb::dev_free(d_sz);
-        if (d_id) bb::dev_free(d_id);
-        if (d_tmp) bb::dev_free(d_tmp);
-        if (d_stage) bb::dev_free(d_stage);
-        if (pin) (void)hipHostFree(pin);
-    }
-};
-
 double img_ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -346,7 +332,10 @@ int img_save(bbh_tree* t, int fd, uint64_t stage_bytes, uint64_t* written) {
     const uint32_t used = empty ? 0u : h.ctr[C_NODES];
     if (!empty && (used > h.cap_nodes || h.ctr[C_N8] > h.cap8 || h.ctr[C_N16] > h.cap16 || h.ctr[C_N32] > h.cap32 || h.ctr[C_ROOT] >= used))
         return bb::fail(BBH_ERR_STATE, "the tree's counters exceed its pools: it cannot be saved");
-    ImgBuffers B;
+    bb::DevScope tmp(nullptr);  // device and pinned buffers of the call (the null stream and blocking copies throughout)
+    uint32_t *d_sz = nullptr, *d_id = nullptr;
+    void* d_tmp = nullptr;
+    uint8_t *d_stage = nullptr, *pin = nullptr;
     ImgHeader H;
     std::memset(&H, 0, sizeof(H));
     std::memcpy(H.magic, IMG_MAGIC, 8);
@@ -358,20 +347,20 @@ int img_save(bbh_tree* t, int fd, uint64_t stage_bytes, uint64_t* written) {
     for (int i = 0; i < 8; ++i) H.stats[i] = h.stats[i];
     uint32_t T = 0;
     if (!empty) {
-        BB_HIP(bb::dev_alloc(&B.d_sz, ((size_t)used + 1) * 4));
-        BB_HIP(bb::dev_alloc(&B.d_id, ((size_t)used + 1) * 4));
-        BB_HIP(hipMemset(B.d_sz + used, 0, 4));
+        BB_HIP(tmp.get(&d_sz, ((size_t)used + 1) * 4));
+        BB_HIP(tmp.get(&d_id, ((size_t)used + 1) * 4));
+        BB_HIP(hipMemset(d_sz + used, 0, 4));
         bb::ProfScope ps("tree_image/save", nullptr);
-        hipLaunchKernelGGL(k_img_size, dim3((used + 255) / 256), dim3(256), 0, 0, (const NodeHdr*)h.node_hdr, used, rows, h.ctr[C_ROOT], B.d_sz);
+        hipLaunchKernelGGL(k_img_size, dim3((used + 255) / 256), dim3(256), 0, 0, (const NodeHdr*)h.node_hdr, used, rows, h.ctr[C_ROOT], d_sz);
         BB_HIP(hipGetLastError());
         size_t tmp_bytes = 0;
-        BB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, B.d_sz, B.d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
-        BB_HIP(bb::dev_alloc(&B.d_tmp, tmp_bytes + 16));
-        BB_HIP(rocprim::exclusive_scan(B.d_tmp, tmp_bytes, B.d_sz, B.d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
+        BB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, d_sz, d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
+        BB_HIP(tmp.get(&d_tmp, tmp_bytes + 16));
+        BB_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_sz, d_id, 0u, (size_t)used + 1, rocprim::plus<uint32_t>(), (hipStream_t)0));
         uint32_t new_root = 0, new_first = NONE;
-        BB_HIP(hipMemcpy(&T, B.d_id + used, 4, hipMemcpyDeviceToHost));
-        BB_HIP(hipMemcpy(&new_root, B.d_id + h.ctr[C_ROOT], 4, hipMemcpyDeviceToHost));
-        if (h.ctr[C_FIRST_LEAF] != NONE && h.ctr[C_FIRST_LEAF] < used) BB_HIP(hipMemcpy(&new_first, B.d_id + h.ctr[C_FIRST_LEAF], 4, hipMemcpyDeviceToHost));
+        BB_HIP(hipMemcpy(&T, d_id + used, 4, hipMemcpyDeviceToHost));
+        BB_HIP(hipMemcpy(&new_root, d_id + h.ctr[C_ROOT], 4, hipMemcpyDeviceToHost));
+        if (h.ctr[C_FIRST_LEAF] != NONE && h.ctr[C_FIRST_LEAF] < used) BB_HIP(hipMemcpy(&new_first, d_id + h.ctr[C_FIRST_LEAF], 4, hipMemcpyDeviceToHost));
         if (T == 0 || T > 0x3FFFFFFFu) return bb::fail(BBH_ERR_STATE, "the tree holds no live node: it cannot be saved");
         H.n_blocks = T; H.n8 = h.ctr[C_N8]; H.n16 = h.ctr[C_N16]; H.n32 = h.ctr[C_N32];
         H.ctr[C_NODES] = T; H.ctr[C_ROOT] = new_root; H.ctr[C_FIRST_LEAF] = new_first;
@@ -391,8 +380,8 @@ int img_save(bbh_tree* t, int fd, uint64_t stage_bytes, uint64_t* written) {
         const uint64_t stage = stage_bytes ? stage_bytes : IMG_DEFAULT_STAGE;
         const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(stage / (IMG_GB * BB), 1), n_groups);
         const size_t buf_bytes = (size_t)per * IMG_GB * BB;
-        BB_HIP(bb::dev_alloc(&B.d_stage, buf_bytes));
-        BB_HIP(hipHostMalloc((void**)&B.pin, buf_bytes, hipHostMallocDefault));
+        BB_HIP(tmp.get(&d_stage, buf_bytes));
+        BB_HIP(tmp.pinned(&pin, buf_bytes));
         note_peak(t, buf_bytes + ((size_t)used + 1) * 8);
         for (uint32_t g = 0; g < n_groups; g += per) {
             const uint32_t lo = g * IMG_GB, hi = (uint32_t)std::min<uint64_t>(T, ((uint64_t)g + per) * IMG_GB);
@@ -400,13 +389,13 @@ int img_save(bbh_tree* t, int fd, uint64_t stage_bytes, uint64_t* written) {
             {
                 bb::ProfScope ps("tree_image/save", nullptr);
                 ps.units((long long)bytes);
-                BB_HIP(hipMemsetAsync(B.d_stage, 0, bytes, nullptr));
+                BB_HIP(hipMemsetAsync(d_stage, 0, bytes, nullptr));
                 const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>((hi - lo) / 4, 1u), 1u << 14);
-                hipLaunchKernelGGL(k_img_pack, dim3(grid), dim3(256), 0, 0, h, used, rows, (const uint32_t*)B.d_sz, (const uint32_t*)B.d_id, T, lo, hi, B.d_stage);
+                hipLaunchKernelGGL(k_img_pack, dim3(grid), dim3(256), 0, 0, h, used, rows, (const uint32_t*)d_sz, (const uint32_t*)d_id, T, lo, hi, d_stage);
                 BB_HIP(hipGetLastError());
             }
-            BB_HIP(hipMemcpy(B.pin, B.d_stage, bytes, hipMemcpyDeviceToHost));
-            BB_TRY(img_write_all(fd, B.pin, bytes));
+            BB_HIP(hipMemcpy(pin, d_stage, bytes, hipMemcpyDeviceToHost));
+            BB_TRY(img_write_all(fd, pin, bytes));
         }
         // the cluster-feature pools go out as they lie: their used prefixes, through the same pinned buffer
         const uint8_t* pools[3] = {(const uint8_t*)h.cf8, (const uint8_t*)h.cf16, (const uint8_t*)h.cf32};
@@ -416,8 +405,8 @@ int img_save(bbh_tree* t, int fd, uint64_t stage_bytes, uint64_t* written) {
         for (int p = 0; p < 3; ++p)
             for (uint64_t off = 0; off < sizes[p]; off += buf_bytes) {
                 const size_t bytes = (size_t)std::min<uint64_t>(buf_bytes, sizes[p] - off);
-                BB_HIP(hipMemcpy(B.pin, pools[p] + off, bytes, hipMemcpyDeviceToHost));
-                BB_TRY(img_write_all(fd, B.pin, bytes));
+                BB_HIP(hipMemcpy(pin, pools[p] + off, bytes, hipMemcpyDeviceToHost));
+                BB_TRY(img_write_all(fd, pin, bytes));
             }
     }
     if (written) *written = H.image_bytes;
@@ -436,23 +425,24 @@ int img_load(bbh_tree* t, int fd, uint64_t base, const ImgHeader& H, uint64_t st
     }
     at += H.tol_bytes;
     if (T == 0) return BBH_OK;
-    ImgBuffers B;
+    bb::DevScope tmp(nullptr);  // (as in img_save)
+    uint8_t *d_stage = nullptr, *pin = nullptr;
     const uint32_t n_groups = (T + IMG_GB - 1) / IMG_GB;
     const uint64_t stage = stage_bytes ? stage_bytes : IMG_DEFAULT_STAGE;
     const uint32_t per = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(stage / (IMG_GB * BB), 1), n_groups);
     const size_t buf_bytes = (size_t)per * IMG_GB * BB;
-    BB_HIP(bb::dev_alloc(&B.d_stage, buf_bytes));
-    BB_HIP(hipHostMalloc((void**)&B.pin, buf_bytes, hipHostMallocDefault));
+    BB_HIP(tmp.get(&d_stage, buf_bytes));
+    BB_HIP(tmp.pinned(&pin, buf_bytes));
     // the cluster-feature pools first (what they hold and the room a first insertion needs, as grow_cf's floor), then the
     // node pools as gc_nodes sizes its new ones: everything live plus a quarter, within what the device has free
     const uint32_t depth = H.ctr[C_DEPTH];
     const uint32_t spare = tiny_pools() ? 8u : 2 * depth + 64;
     const uint32_t caps[3] = {clamp30((uint64_t)H.n8 + spare), clamp30((uint64_t)H.n16 + spare), clamp30((uint64_t)H.n32 + spare)};
-    BB_TRY(grow_pool(h.cf8, 0, (size_t)caps[0] * F));
+    BB_TRY(grow_pool((void**)&h.cf8, 1, 0, (size_t)caps[0] * F));
     h.cap8 = caps[0];
-    BB_TRY(grow_pool(h.cf16, 0, (size_t)caps[1] * F));
+    BB_TRY(grow_pool((void**)&h.cf16, 2, 0, (size_t)caps[1] * F));
     h.cap16 = caps[1];
-    BB_TRY(grow_pool(h.cf32, 0, (size_t)caps[2] * F));
+    BB_TRY(grow_pool((void**)&h.cf32, 4, 0, (size_t)caps[2] * F));
     h.cap32 = caps[2];
     const uint64_t floor_b = (uint64_t)T + (2 * (uint64_t)depth + 8) * node_blocks(rows);
     uint64_t want = std::max<uint64_t>((uint64_t)T + (tiny_pools() ? 0 : (uint64_t)T / 4), floor_b);
@@ -474,12 +464,12 @@ int img_load(bbh_tree* t, int fd, uint64_t base, const ImgHeader& H, uint64_t st
     for (uint32_t g = 0; g < n_groups; g += per) {
         const uint32_t lo = g * IMG_GB, hi = (uint32_t)std::min<uint64_t>(T, ((uint64_t)g + per) * IMG_GB);
         const size_t bytes = (size_t)(hi - lo) * BB;
-        BB_TRY(img_pread_all(fd, B.pin, bytes, at, "nodes"));
-        BB_HIP(hipMemcpy(B.d_stage, B.pin, bytes, hipMemcpyHostToDevice));
+        BB_TRY(img_pread_all(fd, pin, bytes, at, "nodes"));
+        BB_HIP(hipMemcpy(d_stage, pin, bytes, hipMemcpyHostToDevice));
         bb::ProfScope ps("tree_image/load", nullptr);
         ps.units((long long)(bytes + (g == 0 ? sizeof(H) + H.tol_bytes : 0)));
         const uint32_t grid = std::min<uint32_t>(std::max<uint32_t>((hi - lo) / 4, 1u), 1u << 14);
-        hipLaunchKernelGGL(k_img_unpack, dim3(grid), dim3(256), 0, 0, h, T, lo, hi, (const uint8_t*)B.d_stage);
+        hipLaunchKernelGGL(k_img_unpack, dim3(grid), dim3(256), 0, 0, h, T, lo, hi, (const uint8_t*)d_stage);
         BB_HIP(hipGetLastError());
         at += bytes;
     }
@@ -491,8 +481,8 @@ int img_load(bbh_tree* t, int fd, uint64_t base, const ImgHeader& H, uint64_t st
         for (int p = 0; p < 3; ++p)
             for (uint64_t off = 0; off < sizes[p]; off += buf_bytes) {
                 const size_t bytes = (size_t)std::min<uint64_t>(buf_bytes, sizes[p] - off);
-                BB_TRY(img_pread_all(fd, B.pin, bytes, at, "cluster features"));
-                BB_HIP(hipMemcpy(pools[p] + off, B.pin, bytes, hipMemcpyHostToDevice));
+                BB_TRY(img_pread_all(fd, pin, bytes, at, "cluster features"));
+                BB_HIP(hipMemcpy(pools[p] + off, pin, bytes, hipMemcpyHostToDevice));
                 at += bytes;
             }
     }

@@ -22,13 +22,12 @@ static hipError_t sys_alloc_uc(T** p, size_t bytes) {
     }
     return e;
 }
+static void sys_free_uc(void* q) {  // a block of sys_alloc_uc (never cached)
+    if (q) (void)(sys_mem_host() ? hipHostFree(q) : hipFree(q));
+}
 void sys_free(bbh_tree* t) {
-    void* uc[] = {t->sys.rings, t->sys.mail, t->sys.ctl};
-    for (void* q : uc)
-        if (q) (void)(sys_mem_host() ? hipHostFree(q) : hipFree(q));
-    void* ptrs[] = {t->sys.laste, t->sys.busy, t->sys.sent, t->sys.up, t->sys.acks};
-    for (void* q : ptrs)
-        if (q) bb::dev_free(q);
+    for (void* q : {(void*)t->sys.rings, (void*)t->sys.mail, (void*)t->sys.ctl}) sys_free_uc(q);
+    for (void* q : {(void*)t->sys.laste, (void*)t->sys.busy, (void*)t->sys.sent, (void*)t->sys.up, (void*)t->sys.acks}) bb::dev_free(q);
     t->sys = SysDev{};
     t->sys_ring_bytes = 0;
     t->sys_cap_nodes = 0;
@@ -120,8 +119,8 @@ static int sys_prepare(bbh_tree* t, hipStream_t s) {
         if (S.launch_id == 0) S.launch_id = (g_sys_launch.fetch_add(1u) + 1u) & 0x7FFFFFFFu;
     }
     if (ring_bytes > t->sys_ring_bytes || S.G > t->sys_G_alloc) {
-        if (S.rings) (void)(sys_mem_host() ? hipHostFree(S.rings) : hipFree(S.rings));
-        if (S.busy) bb::dev_free(S.busy);
+        sys_free_uc(S.rings);
+        bb::dev_free(S.busy);
         S.rings = nullptr; S.busy = nullptr;
         t->sys_ring_bytes = 0; t->sys_G_alloc = 0;  // (nothing is held until both allocations have succeeded)
         BB_HIP(sys_alloc_uc(&S.rings, ring_bytes));
@@ -131,11 +130,8 @@ static int sys_prepare(bbh_tree* t, hipStream_t s) {
     }
     if (!S.ctl) BB_HIP(sys_alloc_uc(&S.ctl, SC_COUNT * 4));
     if (h.cap_nodes > t->sys_cap_nodes || !S.mail) {
-        if (S.mail) (void)(sys_mem_host() ? hipHostFree(S.mail) : hipFree(S.mail));
-        if (S.sent) bb::dev_free(S.sent);
-        if (S.up) bb::dev_free(S.up);
-        if (S.laste) bb::dev_free(S.laste);
-        if (S.acks) bb::dev_free(S.acks);
+        sys_free_uc(S.mail);
+        bb::dev_free(S.sent); bb::dev_free(S.up); bb::dev_free(S.laste); bb::dev_free(S.acks);
         S.mail = nullptr; S.sent = nullptr; S.up = nullptr; S.laste = nullptr; S.acks = nullptr;
         t->sys_cap_nodes = 0;
         BB_HIP(bb::dev_alloc(&S.laste, (size_t)h.cap_nodes * 4 + 64));
@@ -157,34 +153,27 @@ static int sys_prepare(bbh_tree* t, hipStream_t s) {
 // ids handed out by a launch of the systolic kernel, renumbered into the sequential engines' order (bb_tree_sys.inc)
 static int sys_renumber(bbh_tree* t, uint32_t* out_leaf, uint32_t n, uint32_t base, uint32_t nnew, hipStream_t s) {
     if (out_leaf == nullptr || n == 0 || nnew == 0) return BBH_OK;
+    bb::DevScope tmp(s);
     uint32_t *creator = nullptr, *flag = nullptr, *rank = nullptr, *map = nullptr;
-    void* tmp = nullptr;
-    auto body = [&]() -> int {
-        BB_HIP(bb::dev_alloc(&creator, (size_t)nnew * 4 + 64));
-        BB_HIP(bb::dev_alloc(&flag, (size_t)n * 4 + 64));
-        BB_HIP(bb::dev_alloc(&rank, (size_t)n * 4 + 64));
-        BB_HIP(bb::dev_alloc(&map, (size_t)nnew * 4 + 64));
-        BB_HIP(hipMemsetAsync(creator, 0xFF, (size_t)nnew * 4, s));
-        const dim3 ge((n + 255) / 256), gi((nnew + 255) / 256), blk(256);
-        hipLaunchKernelGGL(k_sys_creator, ge, blk, 0, s, (const uint32_t*)out_leaf, n, base, creator);
-        hipLaunchKernelGGL(k_sys_flag, ge, blk, 0, s, (const uint32_t*)out_leaf, n, base, (const uint32_t*)creator, flag);
-        size_t tmp_bytes = 0;
-        BB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, flag, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
-        BB_HIP(bb::dev_alloc(&tmp, tmp_bytes + 16));
-        BB_HIP(rocprim::exclusive_scan(tmp, tmp_bytes, flag, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
-        hipLaunchKernelGGL(k_sys_map, gi, blk, 0, s, (const uint32_t*)creator, (const uint32_t*)rank, nnew, base, map);
-        hipLaunchKernelGGL(k_sys_apply_out, ge, blk, 0, s, out_leaf, n, base, nnew, (const uint32_t*)map);
-        const uint32_t used = std::min(t->h.cap_nodes, t->h.ctr[C_NODES]);
-        hipLaunchKernelGGL(k_sys_apply_rows, dim3((used + 3) / 4), blk, 0, s, (const NodeHdr*)t->h.node_hdr, t->h.node_rm, used, base, nnew, (const uint32_t*)map);
-        BB_HIP(hipGetLastError());
-        BB_HIP(hipStreamSynchronize(s));
-        return BBH_OK;
-    };
-    const int rc = body();
-    void* ptrs[] = {creator, flag, rank, map, tmp};
-    for (void* q : ptrs)
-        if (q) bb::dev_free(q);
-    return rc;
+    void* d_tmp = nullptr;
+    BB_HIP(tmp.get(&creator, (size_t)nnew * 4 + 64));
+    BB_HIP(tmp.get(&flag, (size_t)n * 4 + 64));
+    BB_HIP(tmp.get(&rank, (size_t)n * 4 + 64));
+    BB_HIP(tmp.get(&map, (size_t)nnew * 4 + 64));
+    BB_HIP(hipMemsetAsync(creator, 0xFF, (size_t)nnew * 4, s));
+    const dim3 ge((n + 255) / 256), gi((nnew + 255) / 256), blk(256);
+    hipLaunchKernelGGL(k_sys_creator, ge, blk, 0, s, (const uint32_t*)out_leaf, n, base, creator);
+    hipLaunchKernelGGL(k_sys_flag, ge, blk, 0, s, (const uint32_t*)out_leaf, n, base, (const uint32_t*)creator, flag);
+    size_t tmp_bytes = 0;
+    BB_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, flag, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
+    BB_HIP(tmp.get(&d_tmp, tmp_bytes + 16));
+    BB_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, flag, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL(k_sys_map, gi, blk, 0, s, (const uint32_t*)creator, (const uint32_t*)rank, nnew, base, map);
+    hipLaunchKernelGGL(k_sys_apply_out, ge, blk, 0, s, out_leaf, n, base, nnew, (const uint32_t*)map);
+    const uint32_t used = std::min(t->h.cap_nodes, t->h.ctr[C_NODES]);
+    hipLaunchKernelGGL(k_sys_apply_rows, dim3((used + 3) / 4), blk, 0, s, (const NodeHdr*)t->h.node_hdr, t->h.node_rm, used, base, nnew, (const uint32_t*)map);
+    BB_HIP(hipGetLastError());
+    return tmp.sync();
 }
 // ---- the kernel's instances ------------------------------------------------------------------------------------------------
 struct SysKernel {
