@@ -48,6 +48,8 @@ _PROTOTYPES = {
     "bbh_isim_from_sum": (_int, [_vp, _i32, _i64, _i64, C.POINTER(_f64), C.POINTER(_int), _vp]),
     "bbh_isim_rows": (_int, [_vp, _i64, _i64, _int, _i64, C.POINTER(_f64), C.POINTER(_int), _vp]),
     "bbh_compl_isim_segments": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "bbh_cluster_stats_segments": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "bbh_dbi_worst_ratios": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "bbh_isim_pair_min_gap": (_int, [_vp, _vp, _i64, _i64, C.POINTER(_f64), _vp]),
     "bbh_most_dissimilar": (
         _int,

@@ -18,7 +18,6 @@ file only keeps what the reference keeps on the host *around* that loop:
 from __future__ import annotations
 
 import io
-import itertools
 import json
 import os
 import pickle
@@ -658,6 +657,39 @@ class BitBirch:
             for p, m in zip(order, lists)
         ]
 
+    def _flat_members(self, sort: bool = True, global_clusters: bool = False) -> tuple[NDArray[np.int64], NDArray[np.int64]]:
+        r"""`get_cluster_mol_ids` as two arrays, without a Python list per cluster: (offsets [k + 1], members
+        [offsets[-1]]); cluster g is members[offsets[g]:offsets[g + 1]]."""
+        lv = self._leaves()
+        order = self._leaf_order(sort)
+        if global_clusters:
+            if self._global_clustering_centroid_labels is None:
+                raise ValueError("Must perform global clustering before fetching global labels")
+            # the leaves of a label one after the other, in leaf order (`_new_ids_from_labels`)
+            labels = np.asarray(self._global_clustering_centroid_labels, dtype=np.int64)[: order.size] - 1
+            n_labels = self._n_global_clusters if self._n_global_clusters is not None else len(np.unique(labels))
+            order = order[np.argsort(labels, kind="stable")]
+            leaf_sizes = (lv["end"] - lv["beg"])[order].astype(np.int64)
+            sizes = np.bincount(labels, weights=(lv["end"] - lv["beg"])[self._leaf_order(sort)], minlength=n_labels).astype(np.int64)
+        else:
+            leaf_sizes = sizes = (lv["end"] - lv["beg"])[order].astype(np.int64)
+        offsets = np.zeros(len(sizes) + 1, dtype=np.int64)
+        np.cumsum(sizes, out=offsets[1:])
+        total = int(offsets[-1])
+        first = np.cumsum(leaf_sizes) - leaf_sizes  # where each leaf's members start in the flat array
+        gather = np.repeat(lv["beg"][order] - first, leaf_sizes) + np.arange(total, dtype=np.int64)
+        return offsets, np.ascontiguousarray(lv["members"][gather], dtype=np.int64)
+
+    def cluster_sets(self, fps, sort: bool = True, global_clusters: bool = False):  # type: ignore[no-untyped-def]
+        r"""The fitted clustering over the packed rows ``fps`` (NumPy array or device tensor, the rows that were fitted, in
+        that order) as `metrics.ClusterSets`: ``jt_isim_chi(tree.cluster_sets(fps))`` scores it in a fixed number of
+        launches.  The clusters are those of `get_cluster_mol_ids` with the same arguments, in the same order."""
+        from bblean_amd.metrics import ClusterSets
+
+        offsets, flat = self._flat_members(sort, global_clusters)
+        nf = self._n_features
+        return ClusterSets(fps, offsets, flat, nf if nf % 8 == 0 and 0 < nf <= fps.shape[1] * 8 else None)
+
     # medoids (reference bitbirch.py:909-967): packed rows take ONE segmented call over all clusters
     def get_medoids_mol_ids(self, fps, sort=True, pack=True, global_clusters=False, input_is_packed=True, n_features=None):  # type: ignore[no-untyped-def]
         from bblean_amd.similarity import _is_dev, _seg_fits, jt_compl_isim_segments, jt_isim_medoid
@@ -670,15 +702,7 @@ class BitBirch:
             nf = nb * 8 if n_features is None else int(n_features)
             sizes = np.fromiter(map(len, members), dtype=np.int64, count=len(members))
             if 0 < nf <= nb * 8 and nf % 8 == 0 and _seg_fits(nf, int(sizes.max())):
-                offsets = np.zeros(len(members) + 1, dtype=np.int64)
-                np.cumsum(sizes, out=offsets[1:])
-                if global_clusters:
-                    flat = np.fromiter(itertools.chain.from_iterable(members), dtype=np.int64, count=int(offsets[-1]))
-                else:  # the member lists are slices of the leaf table: gather them as arrays
-                    lv = self._leaves()
-                    beg = lv["beg"][self._leaf_order(sort)]
-                    flat = lv["members"][np.repeat(beg - offsets[:-1], sizes) + np.arange(int(offsets[-1]), dtype=np.int64)]
-                    flat = np.ascontiguousarray(flat, dtype=np.int64)
+                offsets, flat = self._flat_members(sort, global_clusters)
                 if on_device:
                     import torch
 

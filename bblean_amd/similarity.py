@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import typing as tp
 import warnings
 
 import numpy as np
@@ -43,6 +44,7 @@ __all__ = [
     "jt_assign_packed",
     "jt_dist_matrix_packed",
     "jt_compl_isim_segments",
+    "jt_cluster_stats_segments",
 ]
 
 
@@ -476,15 +478,22 @@ def _seg_host_index(a: object, what: str) -> NDArray[np.int64]:
     return np.ascontiguousarray(arr, dtype=np.int64)
 
 
-def jt_compl_isim_segments(fps, offsets, members=None, n_features=None, return_compl=True):  # type: ignore[no-untyped-def]
-    r"""Complementary iSIM (`jt_compl_isim`) and medoid position (`jt_isim_medoid`) of ``k`` independent sets of packed
-    rows in one call.  Set ``g`` is ``fps[offsets[g]:offsets[g + 1]]``, or ``fps[members[offsets[g]:offsets[g + 1]]]``
-    when ``members`` is given.  Returns ``(positions, compl)``: int64 ``[k]``, the position INSIDE each set of the first
-    minimum of its values (0 for sets of 1 or 2 rows), and float64 ``[offsets[-1]]`` in set order (NaN for sets of 1 or 2
-    rows), or ``None`` with ``return_compl=False``.  Bit for bit the reference's values (_py_similarity.py:65-117).
+class _SegArgs(tp.NamedTuple):
+    r"""The checked arguments of a segmented call (`jt_compl_isim_segments`, `jt_cluster_stats_segments`)."""
 
-    NumPy in -> NumPy out; device tensors in -> device tensors out, on the current stream.  Host rows beyond a slab
-    (`BBHIP_SLAB_KB`) go through in slabs of whole sets, gathered on the host with one `take` per slab."""
+    rows: tp.Any      # 2-D uint8 rows, NumPy or device tensor
+    n_rows: int
+    nb: int
+    stride: int
+    nf: int
+    off: tp.Any       # int64 offsets, NumPy or device tensor
+    k: int
+    mem: tp.Any       # int64 members, NumPy or device tensor, or None
+    total: int        # offsets[-1]
+    on_device: bool   # the call runs on device tensors and the current stream
+
+
+def _seg_args(fps, offsets, members, n_features) -> _SegArgs:  # type: ignore[no-untyped-def]
     dev = _is_dev(fps)
     if dev:
         if fps.dim() != 2 or str(fps.dtype) != "torch.uint8" or fps.stride(1) != 1:
@@ -537,43 +546,137 @@ def jt_compl_isim_segments(fps, offsets, members=None, n_features=None, return_c
             raise ValueError("offsets name more rows than there are")
         if not _seg_fits(nf, int(sizes.max())):
             raise ValueError("a set is too large for exact 64-bit moments: n_features * m * m must stay below 2**63")
-    lib = _lib.load()
-    if dev or off_dev or mem_dev:
-        import torch
-
+    on_device = dev or off_dev or mem_dev
+    if on_device:
         if not dev:
             raise ValueError("offsets / members on the device need fps on the device")
-        d = rows.device
         total = int(off[-1].item()) if off_dev else int(off[-1])
         if total < 0 or total > n_mem:
             raise ValueError("offsets name more rows than there are")
+    else:
+        total = int(off[-1])
+    return _SegArgs(rows, n_rows, nb, stride, nf, off, k, mem, total, on_device)
+
+
+def _seg_slabs(a: _SegArgs):  # type: ignore[no-untyped-def]
+    r"""Host rows beyond a slab (`BBHIP_SLAB_KB`) as slabs of whole sets, a set larger than a slab a slab of its own, each
+    gathered with one `take`: yields (g0, g1, lo, hi, contiguous rows of the sets g0 .. g1, their offsets from 0)."""
+    g0 = 0
+    slab = _slab_rows(a.nb)
+    while g0 < a.k:
+        g1 = int(np.searchsorted(a.off, a.off[g0] + slab, side="right")) - 1
+        g1 = min(a.k, max(g1, g0 + 1))
+        lo, hi = int(a.off[g0]), int(a.off[g1])
+        part = np.ascontiguousarray(a.rows[lo:hi]) if a.mem is None else a.rows.take(a.mem[lo:hi], axis=0)
+        yield g0, g1, lo, hi, part, np.ascontiguousarray(a.off[g0:g1 + 1] - lo)
+        g0 = g1
+
+
+def _seg_one_call(a: _SegArgs) -> bool:
+    slab = _slab_rows(a.nb)
+    return a.total <= slab and (a.mem is None or a.n_rows <= slab)
+
+
+def jt_compl_isim_segments(fps, offsets, members=None, n_features=None, return_compl=True):  # type: ignore[no-untyped-def]
+    r"""Complementary iSIM (`jt_compl_isim`) and medoid position (`jt_isim_medoid`) of ``k`` independent sets of packed
+    rows in one call.  Set ``g`` is ``fps[offsets[g]:offsets[g + 1]]``, or ``fps[members[offsets[g]:offsets[g + 1]]]``
+    when ``members`` is given.  Returns ``(positions, compl)``: int64 ``[k]``, the position INSIDE each set of the first
+    minimum of its values (0 for sets of 1 or 2 rows), and float64 ``[offsets[-1]]`` in set order (NaN for sets of 1 or 2
+    rows), or ``None`` with ``return_compl=False``.  Bit for bit the reference's values (_py_similarity.py:65-117).
+
+    NumPy in -> NumPy out; device tensors in -> device tensors out, on the current stream.  Host rows beyond a slab
+    (`BBHIP_SLAB_KB`) go through in slabs of whole sets, gathered on the host with one `take` per slab."""
+    a = _seg_args(fps, offsets, members, n_features)
+    rows, n_rows, nb, stride, nf, off, k, mem, total = a[:9]
+    lib = _lib.load()
+    if a.on_device:
+        import torch
+
+        d = rows.device
         med_t = torch.empty(k, dtype=torch.int64, device=d)
         compl_t = torch.empty(total, dtype=torch.float64, device=d) if return_compl else None
         st = torch.cuda.current_stream(d).cuda_stream
         _lib.check(lib.bbh_compl_isim_segments(_lib.ptr(rows), n_rows, nb, stride, _lib.ptr(mem), _lib.ptr(off), k, nf,
                                                _lib.ptr(compl_t), _lib.ptr(med_t), st))
         return med_t, compl_t
-    total = int(off[-1])
     med = np.empty(k, dtype=np.int64)
     compl = np.empty(total, dtype=np.float64) if return_compl else None
-    slab = _slab_rows(nb)
-    if total <= slab and (mem is None or n_rows <= slab):
+    if _seg_one_call(a):
         part = rows if mem is not None else rows[:total]
         _lib.check(lib.bbh_compl_isim_segments(part.ctypes.data, len(part), nb, stride, _lib.ptr(mem), off.ctypes.data, k, nf,
                                                _lib.ptr(compl), med.ctypes.data, None))
         return med, compl
-    g0 = 0
-    while g0 < k:  # slabs of whole sets; a set larger than a slab is a slab of its own
-        g1 = int(np.searchsorted(off, off[g0] + slab, side="right")) - 1
-        g1 = min(k, max(g1, g0 + 1))
-        lo, hi = int(off[g0]), int(off[g1])
-        part = np.ascontiguousarray(rows[lo:hi]) if mem is None else rows.take(mem[lo:hi], axis=0)
-        sub = np.ascontiguousarray(off[g0:g1 + 1] - lo)
+    for g0, g1, lo, hi, part, sub in _seg_slabs(a):
         _lib.check(lib.bbh_compl_isim_segments(part.ctypes.data, hi - lo, nb, nb, None, sub.ctypes.data, g1 - g0, nf,
                                                compl[lo:hi].ctypes.data if compl is not None else None,
                                                med[g0:g1].ctypes.data, None))
-        g0 = g1
     return med, compl
+
+
+_STATS = ("centroids", "isim", "dist", "sums")
+
+
+def jt_cluster_stats_segments(fps, offsets, members=None, n_features=None, centrals=None, want=("centroids", "isim", "dist")):  # type: ignore[no-untyped-def]
+    r"""What the clustering indices (`bblean_amd.metrics`) need of ``k`` independent sets of packed rows, in one call.  The
+    sets are given as for `jt_compl_isim_segments`.  Returns a dict with the entries named in ``want``:
+
+    - ``"centroids"``: uint8 ``[k, n_features // 8]``, `centroid` of each set, packed
+    - ``"isim"``: float64 ``[k]``, `jt_isim_packed` of each set (NaN for a set of one row, without a warning)
+    - ``"dist"``: float64 ``[offsets[-1]]`` in set order, ``1 - jt_sim_packed(set, central)`` with the set's centroid as
+      the central, or row ``g`` of ``centrals`` (``[k, >= n_features // 8]`` uint8) when given
+    - ``"sums"``: uint64 ``[k, n_features]``, the column sums of each set
+
+    Bit for bit what those functions give set by set.  NumPy in -> NumPy out; device tensors in -> device tensors out, on
+    the current stream.  Host rows beyond a slab (`BBHIP_SLAB_KB`) go through in slabs of whole sets."""
+    want = tuple(want)
+    if not want or any(w not in _STATS for w in want):
+        raise ValueError(f"want must name some of {_STATS}")
+    a = _seg_args(fps, offsets, members, n_features)
+    rows, n_rows, nb, stride, nf, off, k, mem, total = a[:9]
+    cen, c_stride = None, 0
+    if centrals is not None:
+        if _is_dev(centrals):
+            if not a.on_device:
+                raise ValueError("centrals on the device need fps on the device")
+            ok = centrals.dim() == 2 and str(centrals.dtype) == "torch.uint8" and centrals.stride(1) == 1
+            cen = centrals
+            c_stride = int(cen.stride(0)) if ok else 0
+        else:
+            cen = np.asarray(centrals)
+            ok = cen.ndim == 2 and cen.dtype == np.uint8
+            if ok:
+                cen = np.ascontiguousarray(cen)
+                c_stride = int(cen.shape[1])
+        if not ok or int(cen.shape[0]) != k or int(cen.shape[1]) < nf // 8:
+            raise ValueError("centrals must be a 2-dimensional uint8 array of one packed row per set")
+    lib = _lib.load()
+    shapes = {"centroids": ((k, nf // 8), "uint8"), "isim": ((k,), "float64"), "dist": ((total,), "float64"),
+              "sums": ((k, nf), "uint64")}
+    if a.on_device:
+        import torch
+
+        d = rows.device
+        if cen is not None and not _is_dev(cen):
+            cen = torch.from_numpy(cen).to(d)
+        # (torch has no uint64 arithmetic, the column sums are handed out as int64: the same bits, and they are < 2^63)
+        out_t = {w: torch.empty(shapes[w][0], dtype=getattr(torch, shapes[w][1].replace("uint64", "int64")), device=d)
+                 for w in want}
+        st = torch.cuda.current_stream(d).cuda_stream
+        _lib.check(lib.bbh_cluster_stats_segments(_lib.ptr(rows), n_rows, nb, stride, _lib.ptr(mem), _lib.ptr(off), k, nf,
+                                                  _lib.ptr(cen), c_stride, *(_lib.ptr(out_t.get(w)) for w in _STATS), st))
+        return out_t
+    out = {w: np.empty(shapes[w][0], dtype=shapes[w][1]) for w in want}
+    if _seg_one_call(a):
+        part = rows if mem is not None else rows[:total]
+        _lib.check(lib.bbh_cluster_stats_segments(part.ctypes.data, len(part), nb, stride, _lib.ptr(mem), off.ctypes.data, k, nf,
+                                                  _lib.ptr(cen), c_stride, *(_lib.ptr(out.get(w)) for w in _STATS), None))
+        return out
+    for g0, g1, lo, hi, part, sub in _seg_slabs(a):
+        sl = {"centroids": slice(g0, g1), "isim": slice(g0, g1), "dist": slice(lo, hi), "sums": slice(g0, g1)}
+        _lib.check(lib.bbh_cluster_stats_segments(part.ctypes.data, hi - lo, nb, nb, None, sub.ctypes.data, g1 - g0, nf,
+                                                  cen[g0:g1].ctypes.data if cen is not None else None, c_stride,
+                                                  *(out[w][sl[w]].ctypes.data if w in out else None for w in _STATS), None))
+    return out
 
 
 def _is_packed_u8(fps: object) -> bool:

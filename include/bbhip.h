@@ -154,6 +154,37 @@ int bbh_compl_isim_segments(const uint8_t* rows, int64_t n_rows, int64_t nbytes,
                             const int64_t* members, const int64_t* offsets, int64_t k, int64_t n_features,
                             double* out_compl, int64_t* out_medoid, void* stream);
 
+/* What the clustering indices of bblean/metrics.py need of every cluster, for k sets of packed rows in one call.  Sets,
+ * members, offsets, n_features, residency and every refusal are those of bbh_compl_isim_segments; a refused call writes
+ * nothing.  centrals: optional k x n_features/8 bytes, centrals_stride bytes apart (>= n_features/8; 0 when centrals
+ * is NULL, anything else is BBH_ERR_INVALID).  Every output is optional:
+ *   out_centroids  k x n_features/8 uint8   majority-vote centroid of each set = centroid_from_sum(column sums, m,
+ *                                           pack=True): a bit is set where 2 * count >= m; for m == 1 the row itself
+ *   out_isim       k float64                jt_isim_from_sum(column sums, m) from the exact uint64 moments; NaN for m < 2
+ *   out_dist       offsets[k] float64       set order: 1.0 - inter / max(double(union), 1.0) of every member against its
+ *                                           set's central, centrals[g] when given, else the set's centroid
+ *                                           (1 - jt_sim_packed(clust, central), metrics.py:100 and :134)
+ *   out_sums       k x n_features uint64    column sums of each set in feature order (MSB-first unpacking)
+ * Recorded by bbh_profile_* as "cluster_stats_seg/small" (sets a single wave takes) and "cluster_stats_seg/large",
+ * "cluster_stats_seg" is their sum; units = rows. */
+int bbh_cluster_stats_segments(const uint8_t* rows, int64_t n_rows, int64_t nbytes, int64_t row_stride,
+                               const int64_t* members, const int64_t* offsets, int64_t k, int64_t n_features,
+                               const uint8_t* centrals, int64_t centrals_stride, uint8_t* out_centroids,
+                               double* out_isim, double* out_dist, uint64_t* out_sums, void* stream);
+
+/* Centrals per tile of the all-pairs kernel behind bbh_dbi_worst_ratios (tests sit at this size and next to it). */
+#define BBH_DBI_TILE 64
+
+/* The inner loop of metrics.jt_dbi (bblean/metrics.py:149-158) without a k x k array:
+ *   out_worst[i] = max over j != i of (scatter[i] + scatter[j]) / (1.0 - inter_ij / max(double(union_ij), 1.0)),
+ * starting from 0.0, in IEEE double operations in that order.  A NaN candidate (0 / 0: identical centrals, no scatter)
+ * is skipped as Python's max(max_d, x) skips it, +inf wins; k == 1 gives 0.0.  scatter: k float64, each finite and
+ * >= +0.0.  centrals: k rows of nbytes, stride bytes apart.  out_flags: optional, 2 uint32: [0] the ordered pairs
+ * (i, j != i) with a denominator of 0 under a non-zero numerator, [1] those where both were 0 (the reference raises a
+ * NumPy RuntimeWarning at each).  All pointers host or device.  Recorded as "dbi_pairs"; units = ordered pairs. */
+int bbh_dbi_worst_ratios(const uint8_t* centrals, int64_t k, int64_t nbytes, int64_t stride, const double* scatter,
+                         double* out_worst, uint32_t* out_flags, void* stream);
+
 /* The pair loop of metrics.jt_isim_dunn (bblean/metrics.py:186-199) in one call: min over all pairs i < j of
  * 1 - jt_isim_from_sum(sums[i] + sums[j], sizes[i] + sizes[j]); 1.0 when there are fewer than two clusters.
  * sums: k x n_features uint64 column sums (host or device), sizes: k uint64; out: host double. */
