@@ -588,6 +588,22 @@ class BitBirch:
             cents = unpack_fingerprints(cents, self._n_features)
         return list(cents)
 
+    def centroid_neighbors(self, n_neighbors: int, sort: bool = True) -> tuple[NDArray[np.int64], NDArray[np.float64]]:
+        r"""The `n_neighbors` nearest other centroids of every centroid: ``(ind, dist)``, both ``(K, n_neighbors)``, nearest
+        first.  Positions are those of `get_centroids(sort=sort)`; a centroid is never its own neighbour, an identical other
+        centroid is (at distance 0).  Jaccard distance, ties to the lower position (`similarity.jt_topk_packed`): the
+        neighbour graph of the clustering in ``K x n_neighbors`` memory, on the device."""
+        from bblean_amd.similarity import _topk_check_k, jt_topk_packed
+
+        order = self._leaf_order(sort)
+        k = _topk_check_k(n_neighbors, len(order), True)
+        gather = getattr(self._engine, "gather_centroids", None)
+        cents = gather(order, device_out=True) if gather is not None else np.ascontiguousarray(self._leaves()["cents"][order])
+        ind, dist = jt_topk_packed(cents, cents, k, exclude=np.arange(len(order), dtype=np.int32))
+        if hasattr(ind, "cpu"):
+            ind, dist = ind.cpu().numpy(), dist.cpu().numpy()
+        return ind.astype(np.int64), dist
+
     def get_centroids_mol_ids(self, sort: bool = True, packed: bool = True) -> dict[str, list]:
         r"""(reference bitbirch.py:895-907)"""
         return {

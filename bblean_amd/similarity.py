@@ -43,6 +43,7 @@ __all__ = [
     "jt_best_match_packed",
     "jt_assign_packed",
     "jt_dist_matrix_packed",
+    "jt_topk_packed",
     "jt_compl_isim_segments",
     "jt_cluster_stats_segments",
 ]
@@ -261,6 +262,83 @@ def jt_dist_matrix_packed(queries: object, centroids: object):  # type: ignore[n
         _lib.check(lib.bbh_jt_dist_matrix(q[lo:hi].ctypes.data, hi - lo, q_stride, _lib.ptr(cdev), nc, nb,  # type: ignore[index]
                                           out[lo:hi].ctypes.data, None))
     return out
+
+
+def _topk_check_k(k: object, nc: int, excluding: bool) -> int:
+    r"""The limits of `bbh_jt_topk`, checked before the library is called."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"k must be an integer, got {type(k).__name__}")
+    k = int(k)
+    if k < 1 or k > _lib.BBH_TOPK_MAX:
+        raise ValueError(f"k = {k}: need 1 <= k <= BBH_TOPK_MAX = {_lib.BBH_TOPK_MAX}")
+    most = nc - 1 if excluding else nc
+    if k > most:
+        raise ValueError(f"k = {k} neighbours asked of nc = {nc} rows" + (", each query excluding one" if excluding else ""))
+    return k
+
+
+def jt_topk_packed(queries: object, rows: object, k: int, exclude: object = None, return_counts: bool = False):  # type: ignore[no-untyped-def]
+    r"""The ``k`` nearest rows of ``rows`` for every packed query row, best first: ``(idx int32 (nq, k), dist float64
+    (nq, k))``, equal to ``np.argsort(d, axis=1, kind="stable")[:, :k]`` of ``d = jt_dist_matrix_packed(queries, rows)``
+    and the values of ``d`` there - without the ``nq x nc`` matrix.  The order is `jt_assign_packed`'s (``k = 1`` is its
+    answer), decided on the exact integer counts.  ``dist`` is ``(u - i) / u`` as one float64 division of those counts,
+    0.0 where ``u == 0``; with ``return_counts`` the uint32 intersections and unions follow.
+
+    ``exclude``: optional, one row number per query that this query skips (a value outside ``[0, nc)`` skips nothing);
+    ``jt_topk_packed(c, c, k, exclude=np.arange(len(c)))`` is the neighbour graph of a table.  ``1 <= k <= 64``
+    (``BBH_TOPK_MAX``) and ``k <= nc`` (``nc - 1`` with ``exclude``), else `ValueError`.
+
+    Device tensors in -> device tensors out, on the current stream; host queries larger than a slab (`BBHIP_SLAB_KB`) are
+    staged slab by slab with the table staged once."""
+    q, nq, nb, q_stride, c, nc = _assign_operands(queries, rows)
+    k = _topk_check_k(k, nc, exclude is not None)
+    if exclude is not None and not _is_dev(exclude):
+        exclude = np.ascontiguousarray(exclude)
+        if exclude.ndim != 1 or exclude.dtype.kind not in "iu" or exclude.shape[0] != nq:
+            raise ValueError("exclude must hold one integer row number per query")
+        exclude = np.clip(exclude, -1, nc).astype(np.int32)
+    elif exclude is not None:
+        if exclude.dim() != 1 or int(exclude.shape[0]) != nq or str(exclude.dtype) not in ("torch.int32", "torch.int64"):  # type: ignore[attr-defined]
+            raise ValueError("exclude must hold one integer row number per query")
+    lib = _lib.load()
+    if _is_dev(q):
+        import torch
+
+        dev = q.device  # type: ignore[attr-defined]
+        if not _is_dev(c):
+            c = torch.from_numpy(c).to(dev)
+        ex_t = None
+        if exclude is not None:
+            ex_t = torch.from_numpy(exclude).to(dev) if not _is_dev(exclude) else exclude.clamp(-1, nc).to(torch.int32).contiguous()  # type: ignore[attr-defined]
+        idx_t = torch.empty((nq, k), dtype=torch.int32, device=dev)
+        cnt_t = torch.empty((2, nq, k), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.bbh_jt_topk(_lib.ptr(q), nq, q_stride, _lib.ptr(c), nc, nb, k, _lib.ptr(ex_t), _lib.ptr(idx_t),
+                                   int(cnt_t[0].data_ptr()), int(cnt_t[1].data_ptr()), st))
+        i_t, u_t = cnt_t[0], cnt_t[1]
+        dist_t = torch.where(u_t == 0, 0.0, (u_t - i_t).double() / u_t.double())
+        return (idx_t, dist_t, i_t.view(torch.uint32), u_t.view(torch.uint32)) if return_counts else (idx_t, dist_t)
+    if _is_dev(exclude):
+        exclude = exclude.clamp(-1, nc).to("cpu").numpy().astype(np.int32)  # type: ignore[attr-defined]
+    idx = np.empty((nq, k), dtype=np.int32)
+    inter = np.empty((nq, k), dtype=np.uint32)
+    union = np.empty((nq, k), dtype=np.uint32)
+    slab = _slab_rows(nb)
+    cdev: object = c
+    if nq > slab and not _is_dev(c):  # several calls: the table is staged once
+        import torch
+
+        cdev = torch.from_numpy(c).cuda()
+    for lo in range(0, nq, slab):
+        hi = min(nq, lo + slab)
+        part = q[lo:hi]  # type: ignore[index]
+        _lib.check(lib.bbh_jt_topk(part.ctypes.data, hi - lo, q_stride, _lib.ptr(cdev), nc, nb, k,
+                                   exclude[lo:hi].ctypes.data if exclude is not None else None,
+                                   idx[lo:hi].ctypes.data, inter[lo:hi].ctypes.data, union[lo:hi].ctypes.data, None))
+    u64, i64 = union.astype(np.int64), inter.astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dist = np.where(u64 == 0, 0.0, (u64 - i64).astype(np.float64) / u64.astype(np.float64))
+    return (idx, dist, inter, union) if return_counts else (idx, dist)
 
 
 def jt_sim_matrix_packed(arr: NDArray[np.uint8]) -> NDArray[np.float64]:

@@ -28,7 +28,7 @@ from sklearn.utils.validation import check_is_fitted, validate_data
 from bblean_amd._merges import MergeCriterion
 from bblean_amd.bitbirch import BitBirch as _BitBirch
 from bblean_amd.fingerprints import pack_fingerprints, unpack_fingerprints
-from bblean_amd.similarity import jt_assign_packed, jt_dist_matrix_packed
+from bblean_amd.similarity import _topk_check_k, jt_assign_packed, jt_dist_matrix_packed, jt_topk_packed
 
 __all__ = ["BitBirch", "UnpackedBitBirch"]
 
@@ -159,6 +159,27 @@ class BitBirch(
         check_is_fitted(self)
         return jt_dist_matrix_packed(self._packed_queries(X, input_is_packed, n_features), self._packed_centers)
 
+    def kneighbors(  # type: ignore[no-untyped-def]
+        self, X=None, n_neighbors: int = 5, return_distance: bool = True, input_is_packed: bool = True,
+        n_features: int | None = None
+    ):
+        """The `n_neighbors` nearest subcluster centroids of every row, nearest first (scikit-learn's
+        `KNeighborsMixin.kneighbors`): ``(dist, ind)``, or ``ind`` alone.  ``ind`` holds zero-based positions in
+        `subcluster_centers_` (the label is ``subcluster_labels_[ind]``), ``dist`` the Jaccard distances `transform` gives
+        there; ties go to the lower position, as in `predict`.  ``X=None``: the fitted centroids themselves, each without
+        itself (`centroid_neighbors`).  A device tensor gives device tensors."""
+        check_is_fitted(self)
+        n_centers = int(self._packed_centers.shape[0])
+        if X is None:
+            _topk_check_k(n_neighbors, n_centers, True)
+            ind, dist = self.centroid_neighbors(n_neighbors, sort=True)
+            return (dist, ind) if return_distance else ind
+        k = _topk_check_k(n_neighbors, n_centers, False)
+        dev = _is_dev(X)
+        ind, dist = jt_topk_packed(self._packed_queries(X, input_is_packed, n_features), self._packed_centers, k)
+        ind = ind.long() if dev else ind.astype(np.int64)
+        return (dist, ind) if return_distance else ind
+
     def __sklearn_tags__(self):  # type: ignore[no-untyped-def]
         tags = super().__sklearn_tags__()
         tags.input_tags.sparse = True
@@ -192,3 +213,9 @@ class UnpackedBitBirch(BitBirch):
         self, X, input_is_packed: bool = False, n_features: int | None = None
     ):
         return super().transform(X, input_is_packed=input_is_packed, n_features=n_features)
+
+    def kneighbors(  # type: ignore[no-untyped-def]
+        self, X=None, n_neighbors: int = 5, return_distance: bool = True, input_is_packed: bool = False,
+        n_features: int | None = None
+    ):
+        return super().kneighbors(X, n_neighbors, return_distance, input_is_packed=input_is_packed, n_features=n_features)

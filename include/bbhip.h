@@ -105,6 +105,18 @@ int bbh_jt_assign(const uint8_t* queries, int64_t nq, int64_t q_stride, const ui
 int bbh_jt_dist_matrix(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* cents, int64_t nc,
                        int64_t nbytes, double* out, void* stream);
 
+/* The k nearest rows of a table for every query, best first, in nq x k memory: between bbh_jt_assign (k = 1 gives its
+ * three outputs) and bbh_jt_dist_matrix (the stable argsort of whose row q, cut at k, is out_idx[q * k .. q * k + k)).
+ * The order is bbh_jt_assign's: the smaller (u - i) / u with 0 where u == 0, then the smaller index; it is decided on the
+ * exact integers at every row width, never on rounded quotients.  1 <= nc < 2^31; query rows q_stride bytes apart.
+ * exclude: optional, nq int32; query q skips row exclude[q] (a value outside [0, nc) skips nothing): a table against
+ * itself without the trivial match.  Needs 1 <= k <= BBH_TOPK_MAX and k <= nc (k <= nc - 1 when exclude is given).
+ * out_idx: nq x k int32, row-major; out_inter / out_union: optional nq x k uint32, the pairs' exact counts (true union, 0
+ * allowed).  The result does not depend on the kernel that served the call or on how the grid was split. */
+#define BBH_TOPK_MAX 64
+int bbh_jt_topk(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* rows, int64_t nc, int64_t nbytes,
+                int32_t k, const int32_t* exclude, int32_t* out_idx, uint32_t* out_inter, uint32_t* out_union, void* stream);
+
 /* Test hook: one v_mfma_i32_16x16x64_i8 with the operand lane maps bb_assign.hip documents.
  * a: 16 x 64 int8, b: 64 x 16 int8, d: 16 x 16 int32 = a @ b, all row-major, host or device. */
 int bbh_mfma_i8_probe(const int8_t* a, const int8_t* b, int32_t* d, void* stream);
