@@ -604,6 +604,23 @@ class BitBirch:
             ind, dist = ind.cpu().numpy(), dist.cpu().numpy()
         return ind.astype(np.int64), dist
 
+    def centroid_radius_neighbors(self, radius: float, sort: bool = True) -> tuple[NDArray[np.int64], NDArray[np.int64], NDArray[np.float64]]:
+        r"""Every other centroid within Jaccard distance `radius` of every centroid, as CSR ``(offsets, ind, dist)``:
+        centroid ``p``'s neighbours are ``ind[offsets[p]:offsets[p + 1]]``, in ascending position.  Positions are those of
+        `get_centroids(sort=sort)`; a centroid is never its own neighbour, an identical other centroid is (at distance 0).
+        The threshold twin of `centroid_neighbors` (`similarity.jt_radius_packed`): the graph of the clustering at a merge
+        threshold, in memory proportional to its edges, on the device."""
+        from bblean_amd.similarity import _radius_check, jt_radius_packed
+
+        radius = _radius_check(radius)
+        order = self._leaf_order(sort)
+        gather = getattr(self._engine, "gather_centroids", None)
+        cents = gather(order, device_out=True) if gather is not None else np.ascontiguousarray(self._leaves()["cents"][order])
+        off, ind, dist = jt_radius_packed(cents, cents, radius, exclude=np.arange(len(order), dtype=np.int32))
+        if hasattr(ind, "cpu"):
+            off, ind, dist = off.cpu().numpy(), ind.cpu().numpy(), dist.cpu().numpy()
+        return off, ind.astype(np.int64), dist
+
     def get_centroids_mol_ids(self, sort: bool = True, packed: bool = True) -> dict[str, list]:
         r"""(reference bitbirch.py:895-907)"""
         return {

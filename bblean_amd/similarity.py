@@ -44,6 +44,7 @@ __all__ = [
     "jt_assign_packed",
     "jt_dist_matrix_packed",
     "jt_topk_packed",
+    "jt_radius_packed",
     "jt_compl_isim_segments",
     "jt_cluster_stats_segments",
 ]
@@ -339,6 +340,122 @@ def jt_topk_packed(queries: object, rows: object, k: int, exclude: object = None
     with np.errstate(invalid="ignore", divide="ignore"):
         dist = np.where(u64 == 0, 0.0, (u64 - i64).astype(np.float64) / u64.astype(np.float64))
     return (idx, dist, inter, union) if return_counts else (idx, dist)
+
+
+def _radius_check(radius: object) -> float:
+    r"""A real number that is not NaN, checked before the library is called."""
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)):
+        raise TypeError(f"radius must be a real number, got {type(radius).__name__}")
+    r = float(radius)
+    if r != r:
+        raise ValueError("radius is NaN")
+    return r
+
+
+def _radius_first_capacity(nq: int, nc: int) -> int:
+    r"""Entries the first `bbh_jt_radius` call of a slab has room for: 32 per query and at least 4096, never more than
+    all pairs.  Radius queries on fingerprints usually return a few rows per query, and 32 entries cost 384 bytes of
+    outputs per query; an answer that does not fit costs a second call, at about twice the time."""
+    return min(nq * nc, max(4096, 32 * nq))
+
+
+def jt_radius_packed(queries: object, rows: object, radius: float, exclude: object = None, return_counts: bool = False,  # type: ignore[no-untyped-def]
+                     sort: bool = False):
+    r"""Every row of ``rows`` within Jaccard distance ``radius`` of every packed query row, as CSR: ``(offsets int64
+    (nq + 1,), idx int32 (total,), dist float64 (total,))``; query ``q``'s hits are ``idx[offsets[q]:offsets[q + 1]]``,
+    equal to ``np.flatnonzero(d[q] <= radius)`` of ``d = jt_dist_matrix_packed(queries, rows)`` and in that (ascending)
+    order - without the ``nq x nc`` matrix.  A pair at ``radius`` bit for bit is a hit; ``radius < 0`` gives nothing,
+    ``radius >= 1`` every row.  ``dist`` is ``(u - i) / u`` as one float64 division of the exact counts, 0.0 where
+    ``u == 0``; with ``return_counts`` the uint32 intersections and unions follow.
+
+    ``exclude``: optional, one row number per query that this query skips (a value outside ``[0, nc)`` skips nothing);
+    ``jt_radius_packed(c, c, r, exclude=np.arange(len(c)))`` is the threshold graph of a table.  ``sort=True`` orders every
+    query's hits by (distance, row number) instead: its first ``k`` entries are then `jt_topk_packed`'s.
+
+    Device tensors in -> device tensors out, on the current stream (the call synchronises it: the size of the answer
+    decides what is allocated).  Host queries go slab by slab (`BBHIP_SLAB_KB`) with the table staged once.  Every slab
+    takes one library call when the answer fits the first capacity (`_radius_first_capacity`: 32 entries per query, at
+    least 4096), else a second one at the exact size."""
+    q, nq, nb, q_stride, c, nc = _assign_operands(queries, rows)
+    radius = _radius_check(radius)
+    if exclude is not None and not _is_dev(exclude):
+        exclude = np.ascontiguousarray(exclude)
+        if exclude.ndim != 1 or exclude.dtype.kind not in "iu" or exclude.shape[0] != nq:
+            raise ValueError("exclude must hold one integer row number per query")
+        exclude = np.clip(exclude, -1, nc).astype(np.int32)
+    elif exclude is not None:
+        if exclude.dim() != 1 or int(exclude.shape[0]) != nq or str(exclude.dtype) not in ("torch.int32", "torch.int64"):  # type: ignore[attr-defined]
+            raise ValueError("exclude must hold one integer row number per query")
+    lib = _lib.load()
+    total = np.zeros(1, dtype=np.int64)
+    if _is_dev(q):
+        import torch
+
+        dev = q.device  # type: ignore[attr-defined]
+        if not _is_dev(c):
+            c = torch.from_numpy(c).to(dev)
+        ex_t = None
+        if exclude is not None:
+            ex_t = torch.from_numpy(exclude).to(dev) if not _is_dev(exclude) else exclude.clamp(-1, nc).to(torch.int32).contiguous()  # type: ignore[attr-defined]
+        off_t = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        cap = _radius_first_capacity(nq, nc)
+        while True:
+            idx_t = torch.empty(cap, dtype=torch.int32, device=dev)
+            cnt_t = torch.empty((2, cap), dtype=torch.int32, device=dev)
+            _lib.check(lib.bbh_jt_radius(_lib.ptr(q), nq, q_stride, _lib.ptr(c), nc, nb, radius, _lib.ptr(ex_t), cap,
+                                         _lib.ptr(off_t), total.ctypes.data, _lib.ptr(idx_t) if cap else None,
+                                         int(cnt_t[0].data_ptr()) if cap else None, int(cnt_t[1].data_ptr()) if cap else None, st))
+            n = int(total[0])
+            if n <= cap:
+                break
+            cap = n
+        idx_t, i_t, u_t = idx_t[:n], cnt_t[0, :n], cnt_t[1, :n]
+        dist_t = torch.where(u_t == 0, 0.0, (u_t - i_t).double() / u_t.double())
+        if sort and n:
+            seg = torch.repeat_interleave(torch.arange(nq, device=dev), off_t[1:] - off_t[:-1])
+            o1 = torch.sort(dist_t, stable=True).indices
+            order = o1[torch.sort(seg[o1], stable=True).indices]
+            idx_t, dist_t, i_t, u_t = idx_t[order], dist_t[order], i_t[order], u_t[order]
+        return (off_t, idx_t, dist_t, i_t.view(torch.uint32), u_t.view(torch.uint32)) if return_counts else (off_t, idx_t, dist_t)
+    if _is_dev(exclude):
+        exclude = exclude.clamp(-1, nc).to("cpu").numpy().astype(np.int32)  # type: ignore[attr-defined]
+    slab = _slab_rows(nb)
+    cdev: object = c
+    if nq > slab and not _is_dev(c):  # several calls: the table is staged once
+        import torch
+
+        cdev = torch.from_numpy(c).cuda()
+    offsets = np.zeros(nq + 1, dtype=np.int64)
+    parts: list[tuple[np.ndarray, np.ndarray, np.ndarray]] = []
+    for lo in range(0, nq, slab):
+        hi = min(nq, lo + slab)
+        part = q[lo:hi]  # type: ignore[index]
+        off = np.empty(hi - lo + 1, dtype=np.int64)
+        cap = _radius_first_capacity(hi - lo, nc)
+        while True:
+            out = np.empty((3, cap), dtype=np.uint32)
+            _lib.check(lib.bbh_jt_radius(part.ctypes.data, hi - lo, q_stride, _lib.ptr(cdev), nc, nb, radius,
+                                         exclude[lo:hi].ctypes.data if exclude is not None else None, cap, off.ctypes.data,
+                                         total.ctypes.data, out[0].ctypes.data if cap else None,
+                                         out[1].ctypes.data if cap else None, out[2].ctypes.data if cap else None, None))
+            n = int(total[0])
+            if n <= cap:
+                break
+            cap = n
+        offsets[lo + 1:hi + 1] = offsets[lo] + off[1:]
+        parts.append((out[0, :n].view(np.int32), out[1, :n], out[2, :n]))
+    if parts:
+        idx, inter, union = (np.concatenate([p[j] for p in parts]) for j in range(3))
+    else:
+        idx, inter, union = np.empty(0, np.int32), np.empty(0, np.uint32), np.empty(0, np.uint32)
+    u64, i64 = union.astype(np.int64), inter.astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        dist = np.where(u64 == 0, 0.0, (u64 - i64).astype(np.float64) / u64.astype(np.float64))
+    if sort and len(idx):
+        order = np.lexsort((dist, np.repeat(np.arange(nq), np.diff(offsets))))  # stable: equal distances keep the index order
+        idx, dist, inter, union = idx[order], dist[order], inter[order], union[order]
+    return (offsets, idx, dist, inter, union) if return_counts else (offsets, idx, dist)
 
 
 def jt_sim_matrix_packed(arr: NDArray[np.uint8]) -> NDArray[np.float64]:

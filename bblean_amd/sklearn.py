@@ -28,7 +28,14 @@ from sklearn.utils.validation import check_is_fitted, validate_data
 from bblean_amd._merges import MergeCriterion
 from bblean_amd.bitbirch import BitBirch as _BitBirch
 from bblean_amd.fingerprints import pack_fingerprints, unpack_fingerprints
-from bblean_amd.similarity import _topk_check_k, jt_assign_packed, jt_dist_matrix_packed, jt_topk_packed
+from bblean_amd.similarity import (
+    _radius_check,
+    _topk_check_k,
+    jt_assign_packed,
+    jt_dist_matrix_packed,
+    jt_radius_packed,
+    jt_topk_packed,
+)
 
 __all__ = ["BitBirch", "UnpackedBitBirch"]
 
@@ -180,6 +187,60 @@ class BitBirch(
         ind = ind.long() if dev else ind.astype(np.int64)
         return (dist, ind) if return_distance else ind
 
+    def _radius_csr(self, X, radius, sort: bool, input_is_packed: bool, n_features: int | None):  # type: ignore[no-untyped-def]
+        r"""The CSR triple of `jt_radius_packed` for `X` (None: the fitted centroids, each without itself) against the
+        fitted centroids; ``radius=None`` is the merge threshold as a distance, ``1.0 - threshold``."""
+        check_is_fitted(self)
+        radius = _radius_check(1.0 - self.threshold if radius is None else radius)
+        cents = self._packed_centers
+        if X is None:
+            return jt_radius_packed(cents, cents, radius, exclude=np.arange(int(cents.shape[0]), dtype=np.int32), sort=sort)
+        return jt_radius_packed(self._packed_queries(X, input_is_packed, n_features), cents, radius, sort=sort)
+
+    def radius_neighbors(  # type: ignore[no-untyped-def]
+        self, X=None, radius: float | None = None, return_distance: bool = True, sort_results: bool = False,
+        input_is_packed: bool = True, n_features: int | None = None
+    ):
+        """Every subcluster centroid within Jaccard distance `radius` of every row (scikit-learn's
+        `RadiusNeighborsMixin.radius_neighbors`): ``(dist, ind)``, or ``ind`` alone, each an object array with one array
+        per row.  ``ind`` holds int64 zero-based positions in `subcluster_centers_`, ascending (``sort_results=True``:
+        by distance, then position; it needs ``return_distance=True``, as in scikit-learn); ``dist`` the distances
+        `transform` gives there, and a centroid at `radius` exactly is in.  ``radius=None``: ``1.0 - threshold``, the
+        merge threshold.  ``X=None``: the fitted centroids themselves, each without itself.
+
+        A device tensor does not get object arrays: it gives the CSR triple ``(offsets int64 (n + 1,), ind int64, dist)``
+        as device tensors (``(offsets, ind)`` without distances), row ``p``'s part being ``offsets[p]:offsets[p + 1]``."""
+        if sort_results and not return_distance:
+            raise ValueError("return_distance must be True if sort_results is True")
+        dev = _is_dev(X)
+        off, ind, dist = self._radius_csr(X, radius, sort_results, input_is_packed, n_features)
+        if dev:
+            return (off, ind.long(), dist) if return_distance else (off, ind.long())
+        if _is_dev(ind):
+            off, ind, dist = off.cpu().numpy(), ind.cpu().numpy(), dist.cpu().numpy()
+        ind = ind.astype(np.int64)
+        inds, dists = np.empty(len(off) - 1, dtype=object), np.empty(len(off) - 1, dtype=object)
+        for p in range(len(off) - 1):
+            inds[p], dists[p] = ind[off[p]:off[p + 1]], dist[off[p]:off[p + 1]]
+        return (dists, inds) if return_distance else inds
+
+    def radius_neighbors_graph(  # type: ignore[no-untyped-def]
+        self, X=None, radius: float | None = None, mode: str = "connectivity", input_is_packed: bool = True,
+        n_features: int | None = None
+    ):
+        """`radius_neighbors` as a `scipy.sparse.csr_matrix` of shape ``(n_queries, n_centroids)`` (scikit-learn's
+        `radius_neighbors_graph`): ones where a centroid is within `radius` (``mode="connectivity"``), or the distances
+        there (``mode="distance"``; a centroid at distance 0 is a stored zero).  Always on the host."""
+        from scipy.sparse import csr_matrix
+
+        if mode not in ("connectivity", "distance"):
+            raise ValueError(f'mode must be "connectivity" or "distance", got {mode!r}')
+        off, ind, dist = self._radius_csr(X, radius, False, input_is_packed, n_features)
+        if _is_dev(ind):
+            off, ind, dist = off.cpu().numpy(), ind.cpu().numpy(), dist.cpu().numpy()
+        data = dist if mode == "distance" else np.ones(len(ind), dtype=np.float64)
+        return csr_matrix((data, ind.astype(np.int64), off), shape=(len(off) - 1, int(self._packed_centers.shape[0])))
+
     def __sklearn_tags__(self):  # type: ignore[no-untyped-def]
         tags = super().__sklearn_tags__()
         tags.input_tags.sparse = True
@@ -219,3 +280,16 @@ class UnpackedBitBirch(BitBirch):
         n_features: int | None = None
     ):
         return super().kneighbors(X, n_neighbors, return_distance, input_is_packed=input_is_packed, n_features=n_features)
+
+    def radius_neighbors(  # type: ignore[no-untyped-def]
+        self, X=None, radius: float | None = None, return_distance: bool = True, sort_results: bool = False,
+        input_is_packed: bool = False, n_features: int | None = None
+    ):
+        return super().radius_neighbors(X, radius, return_distance, sort_results, input_is_packed=input_is_packed,
+                                        n_features=n_features)
+
+    def radius_neighbors_graph(  # type: ignore[no-untyped-def]
+        self, X=None, radius: float | None = None, mode: str = "connectivity", input_is_packed: bool = False,
+        n_features: int | None = None
+    ):
+        return super().radius_neighbors_graph(X, radius, mode, input_is_packed=input_is_packed, n_features=n_features)

@@ -117,6 +117,24 @@ int bbh_jt_dist_matrix(const uint8_t* queries, int64_t nq, int64_t q_stride, con
 int bbh_jt_topk(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* rows, int64_t nc, int64_t nbytes,
                 int32_t k, const int32_t* exclude, int32_t* out_idx, uint32_t* out_inter, uint32_t* out_union, void* stream);
 
+/* Every row of a table within a Jaccard distance of every query, as CSR: the threshold twin of bbh_jt_topk.  A pair
+ * (query q, row m) with i = popcount(q & m) and u = |q| + |m| - i is a hit iff d <= radius in float64, where d is
+ * bbh_jt_dist_matrix's value: (u - i) / u as one float64 division, 0.0 where u == 0.  Query q's hits are exactly
+ * flatnonzero(dist_matrix[q] <= radius), in ascending row index, at every row width: a pair at the radius bit for bit is
+ * a hit, one ulp above is not; radius < 0 gives nothing, radius >= 1 every row.  1 <= nc < 2^31; query rows q_stride bytes
+ * apart.  exclude: optional, nq int32; query q skips row exclude[q] (a value outside [0, nc) skips nothing).
+ * The size of the answer is not known before the call, so the call works like snprintf.  It always writes out_offsets
+ * (nq + 1 int64, out_offsets[0] = 0) and *out_total = out_offsets[nq], which may exceed 2^31.  If total <= capacity it also
+ * writes the first total entries of out_idx (int32 row numbers) and of the optional out_inter / out_union (uint32 exact
+ * counts, true union, 0 allowed), query q's at [out_offsets[q], out_offsets[q + 1]), and nothing beyond them.  If total >
+ * capacity it writes none of the three and still returns BBH_OK: the caller compares *out_total with capacity and calls
+ * again.  capacity = 0 with null outputs is the pure count.  BBH_ERR_INVALID, with nothing written: a NaN radius, capacity <
+ * 0, a null out_offsets or out_total, capacity > 0 with a null out_idx.  Every pointer may be host or device memory.  The
+ * call synchronises the stream.  The result does not depend on the kernel that served the call or on how the grid was split. */
+int bbh_jt_radius(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* rows, int64_t nc, int64_t nbytes,
+                  double radius, const int32_t* exclude, int64_t capacity, int64_t* out_offsets, int64_t* out_total,
+                  int32_t* out_idx, uint32_t* out_inter, uint32_t* out_union, void* stream);
+
 /* Test hook: one v_mfma_i32_16x16x64_i8 with the operand lane maps bb_assign.hip documents.
  * a: 16 x 64 int8, b: 64 x 16 int8, d: 16 x 16 int32 = a @ b, all row-major, host or device. */
 int bbh_mfma_i8_probe(const int8_t* a, const int8_t* b, int32_t* d, void* stream);
