@@ -2393,6 +2393,8 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
                 // jt_isim_from_sum(new_ls, new_n) >= threshold (_merges.py:56-69).  The quotient a / d is only formed when
                 // a is within 2^-48 of threshold * d: outside that band the correctly rounded quotient is on the same side
                 // of the threshold as the exact one (similarity.cpp:297-300 operation order for a and d).
+                // tests/test_hip_tree_thresholds.py walks a ladder of thresholds through this band (0, +-1, +-8, +-24, +-40,
+                // +-1000 ulps around quotients that thousands of merges hit exactly) against the oracle.
                 if (s1n == 0ull) {
                     acc = 1.0 >= thr;
                 } else {

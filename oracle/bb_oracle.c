@@ -284,6 +284,9 @@ struct bbo_tree {
     uint32_t last_leaf_id;
     int last_merged;
     uint64_t stats[7];
+    /* bbo_tree_edge_counts: observed only, no decision reads them */
+    uint64_t edge[4];
+    uint64_t tie_depth[8]; /* edge[3] by the depth of the node searched (root = 1; the last entry takes 8 and deeper) */
 };
 
 static Sub* sub_new(const bbo_tree* t) {
@@ -418,45 +421,67 @@ static double radius_compl_sub(const bbo_tree* t, const Sub* s) {
     return r;
 }
 
+/* a >= b and a < b as the criteria write them; *eq notes a comparison of two equal values (bbo_tree_edge_counts) */
+static inline int cmp_ge(double a, double b, int* eq) {
+    if (a == b) *eq = 1;
+    return a >= b;
+}
+
+static inline int cmp_lt(double a, double b, int* eq) {
+    if (a == b) *eq = 1;
+    return a < b;
+}
+
 /* merge_accept_fn(threshold, new_ls, new_n, old_ls, nom_ls, old_n, nom_n), _merges.py */
-static int tree_accept(const bbo_tree* t, const uint32_t* new_ls, uint64_t new_n,
-                       const Sub* old, uint64_t nom_n) {
+static int tree_accept_eq(const bbo_tree* t, const uint32_t* new_ls, uint64_t new_n,
+                          const Sub* old, uint64_t nom_n, int* eq) {
     uint64_t s1, s2;
     switch (t->crit) {
         case BBO_CRIT_DIAMETER:
             moments_u32(new_ls, t->F, &s1, &s2);
-            return isim_from_moments(s1, s2, new_n) >= t->thr;
+            return cmp_ge(isim_from_moments(s1, s2, new_n), t->thr, eq);
         case BBO_CRIT_RADIUS:
-            return radius_compl_u32(new_ls, t->F, new_n) >= t->thr;
+            return cmp_ge(radius_compl_u32(new_ls, t->F, new_n), t->thr, eq);
         case BBO_CRIT_TOL_DIAMETER: {
             moments_u32(new_ls, t->F, &s1, &s2);
             double new_dc = isim_from_moments(s1, s2, new_n);
-            if (new_dc < t->thr) return 0;
+            if (cmp_lt(new_dc, t->thr, eq)) return 0;
             if (old->n == 1) return 1;
             moments_sub(t, old, &s1, &s2);
             double old_dc = isim_from_moments(s1, s2, old->n);
-            return new_dc >= old_dc - tol_lookup(t->tol_table, t->tol_len, (int64_t)old->n);
+            return cmp_ge(new_dc, old_dc - tol_lookup(t->tol_table, t->tol_len, (int64_t)old->n), eq);
         }
         case BBO_CRIT_TOL_RADIUS: {
             double new_rc = radius_compl_u32(new_ls, t->F, new_n);
-            if (new_rc < t->thr) return 0;
+            if (cmp_lt(new_rc, t->thr, eq)) return 0;
             if (old->n == 1) return 1;
             double old_rc = radius_compl_sub(t, old);
-            return new_rc >= old_rc - tol_lookup(t->tol_table, t->tol_len, (int64_t)old->n);
+            return cmp_ge(new_rc, old_rc - tol_lookup(t->tol_table, t->tol_len, (int64_t)old->n), eq);
         }
         case BBO_CRIT_TOL_LEGACY: {
             moments_u32(new_ls, t->F, &s1, &s2);
             double new_dc = isim_from_moments(s1, s2, new_n);
-            if (new_dc < t->thr) return 0;
+            if (cmp_lt(new_dc, t->thr, eq)) return 0;
             if (old->n == 1 || nom_n != 1) return 1;
             moments_sub(t, old, &s1, &s2);
             double old_dc = isim_from_moments(s1, s2, old->n);
-            return (new_dc * (double)new_n - old_dc * (double)(old->n - 1)) / 2 >=
-                   old_dc - t->tolerance;
+            return cmp_ge((new_dc * (double)new_n - old_dc * (double)(old->n - 1)) / 2,
+                          old_dc - t->tolerance, eq);
         }
         default:
             return 0;
     }
+}
+
+static int tree_accept(bbo_tree* t, const uint32_t* new_ls, uint64_t new_n, const Sub* old,
+                       uint64_t nom_n) {
+    int eq = 0;
+    int acc = tree_accept_eq(t, new_ls, new_n, old, nom_n, &eq);
+    if (t->crit >= BBO_CRIT_DIAMETER && t->crit <= BBO_CRIT_TOL_LEGACY) {
+        t->edge[0]++;
+        t->edge[1] += (uint64_t)eq;
+    }
+    return acc;
 }
 
 /* _BFSubcluster.merge_subcluster, bitbirch.py:507-526 */
@@ -533,13 +558,28 @@ static int node_insert(bbo_tree* t, Node* node, Sub* S, int depth) {
     uint32_t cs = popcount_row(S->cent, t->nbytes);
     int best = 0;
     double best_sim = -1.0;
+    /* (the maximum's (inter, union) pair, rows that tie with it, a tie of another pair: bbo_tree_edge_counts) */
+    uint32_t best_inter = 0, best_union = 0;
+    int ties = 0, ties_differ = 0;
     for (int i = 0; i < node->len; ++i) {
         uint32_t inter = and_popcount_row(node->cents + (size_t)i * t->nbytes, S->cent, t->nbytes);
         double sim = jt_from_counts(inter, node->cards[i], cs);
+        uint32_t uni = node->cards[i] + cs - inter;
         if (sim > best_sim) { /* np.argmax: first maximum, bitbirch.py:320 */
             best_sim = sim;
             best = i;
+            best_inter = inter;
+            best_union = uni;
+            ties = ties_differ = 0;
+        } else if (sim == best_sim) {
+            ties++;
+            if (inter != best_inter || uni != best_union) ties_differ = 1;
         }
+    }
+    if (best_sim > 0.0 && ties > 0) {
+        t->edge[2]++;
+        t->edge[3] += (uint64_t)ties_differ;
+        t->tie_depth[depth < 8 ? depth - 1 : 7] += (uint64_t)ties_differ;
     }
     t->stats[0]++;
     t->stats[1] += (uint64_t)node->len;
@@ -641,6 +681,8 @@ void bbo_tree_reset(bbo_tree* t) {
     t->next_id = 0;
     t->num_fitted = 0;
     memset(t->stats, 0, sizeof(t->stats)); /* the counters restart with the tree, as the engine's do */
+    memset(t->edge, 0, sizeof(t->edge));
+    memset(t->tie_depth, 0, sizeof(t->tie_depth));
 }
 
 void bbo_tree_destroy(bbo_tree* t) {
@@ -780,3 +822,7 @@ int bbo_tree_gather_buffers(const bbo_tree* t, const int64_t* positions, int64_t
 }
 
 void bbo_tree_stats(const bbo_tree* t, uint64_t* out7) { memcpy(out7, t->stats, sizeof(t->stats)); }
+
+void bbo_tree_edge_counts(const bbo_tree* t, uint64_t* out4) { memcpy(out4, t->edge, sizeof(t->edge)); }
+
+void bbo_tree_tie_depths(const bbo_tree* t, uint64_t* out8) { memcpy(out8, t->tie_depth, sizeof(t->tie_depth)); }

@@ -102,6 +102,14 @@ int bbo_tree_gather_buffers(const bbo_tree* t, const int64_t* positions, int64_t
 /* counters: [0]=similarity calls, [1]=rows compared, [2]=merges, [3]=appends,
  * [4]=splits, [5]=nodes, [6]=max depth seen */
 void bbo_tree_stats(const bbo_tree* t, uint64_t* out7);
+/* how often the tree sat on an edge, since create or reset; no decision reads them:
+ * [0]=merge decisions evaluated (never-merge evaluates none), [1]=those in which a >= or < of the criterion compared two
+ * equal float64 values, [2]=best-row searches whose maximum similarity is > 0 and attained by more than one row,
+ * [3]=those of [2] whose tied rows have different (intersection, union) pairs */
+void bbo_tree_edge_counts(const bbo_tree* t, uint64_t* out4);
+/* [3] of the edge counts by the depth of the node that was searched: out8[d - 1] for depth d (the root is 1), the last
+ * entry for 8 and deeper.  Depths below the tree's deepest are internal levels. */
+void bbo_tree_tie_depths(const bbo_tree* t, uint64_t* out8);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,8 @@ def oracle_lib() -> C.CDLL:
         "bbo_tree_export_leaves": (None, [vp, vp, vp, vp, vp]),
         "bbo_tree_gather_buffers": (C.c_int, [vp, vp, i64, i32, vp]),
         "bbo_tree_stats": (None, [vp, vp]),
+        "bbo_tree_edge_counts": (None, [vp, vp]),
+        "bbo_tree_tie_depths": (None, [vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)
@@ -118,6 +120,19 @@ class OracleEngine:
         out = np.zeros(8, dtype=np.uint64)
         self.lib.bbo_tree_stats(self._h, out.ctypes.data)
         return out
+
+    def edge_counts(self):
+        r"""[merge decisions, those with a comparison of two equal values, best-row searches with a tied maximum > 0,
+        those tied between different (inter, union) pairs], since create or reset."""
+        out = np.zeros(4, dtype=np.uint64)
+        self.lib.bbo_tree_edge_counts(self._h, out.ctypes.data)
+        return [int(v) for v in out]
+
+    def tie_depths(self):
+        r"""edge_counts()[3] by the depth of the node searched: [depth 1 (the root), depth 2, ..., depth 8 and deeper]."""
+        out = np.zeros(8, dtype=np.uint64)
+        self.lib.bbo_tree_tie_depths(self._h, out.ctypes.data)
+        return [int(v) for v in out]
 
     def close(self):
         if self._h:
