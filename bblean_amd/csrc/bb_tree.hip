@@ -134,7 +134,8 @@ struct TreeDev {
     unsigned long long phase[16];  // shader-clock cycles per phase (thread 0), debug; [8..] descent detail
     unsigned long long sphase[8]; // same, inside split_node
     unsigned long long splitprof[10];  // pipelined kernel (phase-timer build): the leaf split's phases (split_node's SPH marks), splits, cycles
-    unsigned long long mlprof[8];  // multi-level router (phase-timer build): tracking-CF cache misses, levels committed
+    unsigned long long mlprof[8];  // multi-level router (phase-timer build): tracking-CF cache misses, levels committed; [6]: forwarded
+                                   // intersections the single-level router consumed (pipe_fwd)
     unsigned long long rprof[4];   // router (phase-timer build): cycles waiting for a ring entry / wave 2's stamp / a leaf's pending jobs / a full leaf's decision
     // job of the next launch
     const uint8_t* rows;
@@ -2985,6 +2986,7 @@ static void print_pipe_phases(const bbh_tree* t) {
     const double n = (double)(t->h.stats[2] + t->h.stats[3]);
     fprintf(stderr, "[bbhip pipe phases, per insert]");
     for (int i = 0; i < 16; ++i) fprintf(stderr, " %s=%.*f", nm[i], i < 12 ? 0 : 4, n > 0 ? (double)t->h.phase[i] / n : 0.0);
+    fprintf(stderr, " #router-fwd=%.4f", n > 0 ? (double)t->h.mlprof[6] / n : 0.0);
     static const char* kd[3] = {"pre-compared, best row folded", "own", "pre-compared, every row checked"};
     fprintf(stderr, "\n[bbhip pipe leaf compares]");
     for (int i = 0; i < 3; ++i)

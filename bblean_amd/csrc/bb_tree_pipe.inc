@@ -482,14 +482,25 @@ __device__ __forceinline__ void pipe_choose(LA unsigned char* L, uint32_t cent_o
     pipe_argmax<RPL>(L, card_off, len, pop, inter, j_out, inter_out);
 }
 
+// A FORWARDED intersection (nodes of one row per lane): the chain wave that has just rewritten a row of its slot already holds
+// the next element's row when that element is known, and counts popc(new row & next element) from the registers the row was
+// written from - together with the row's popcount, in the same reduction.  The value is kept in the row's lane as
+// pipe_fwd(key, value), key = the number (+ 1: never zero) of the element it is for; every other lane holds 0.  The compare of
+// exactly that element takes it for that row whatever the pre-compare's tag says: the row has a single writer and is not
+// written again before this compare, so it is the integer the `while (m)` loop of pipe_choose would count from LDS.
+__device__ __forceinline__ uint32_t pipe_fwd(uint32_t key, uint32_t val) { return (key << 12) | val; }  // (val <= 2048, key < 2^20)
+
 // The same for a node of one row per lane whose owner keeps the rows' popcounts and versions in registers (lane r: row r).
 __device__ __forceinline__ void pipe_choose_rv(LA unsigned char* L, uint32_t cent_off, uint32_t len, uint32_t pop, uint32_t xd, uint32_t pre_off,
-                                               uint32_t card, uint32_t ver, uint32_t& j_out, uint32_t& inter_out, uint32_t& n_stale) {
+                                               uint32_t card, uint32_t ver, uint32_t fwd, uint32_t fkey, uint32_t& j_out, uint32_t& inter_out,
+                                               uint32_t& n_stale, uint32_t& n_fwd) {
     const uint32_t lane = (uint32_t)ftid() & 63u;
     const uint32_t en = *(LA uint32_t*)(L + pre_off + lane * 4);
-    uint32_t inter = en & 0xFFFu;
+    const bool fw = (fwd >> 12) == fkey;
+    uint32_t inter = fw ? fwd & 0xFFFu : en & 0xFFFu;
     const bool valid = en != PRE_INVALID && (en >> 12) == (ver & 0xFFFFFu);
-    u64 m = __ballot(lane < len && !valid);
+    n_fwd += __ballot(fw && !valid) != 0ull ? 1u : 0u;
+    u64 m = __ballot(lane < len && !valid && !fw);
     while (m != 0ull) {
         const int l = __ffsll((long long)m) - 1;
         m &= m - 1ull;
@@ -1111,7 +1122,9 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
     // wave reads (the rows, their versions for wave 2) is still written to the slot.
     constexpr bool RV = RPL == 1;
     uint32_t r_link = NONE, r_n = 0, r_ts = 0, r_clen = 0, r_pend = 0, r_card = 0, r_ver = 0;
-    (void)r_link; (void)r_n; (void)r_ts; (void)r_clen; (void)r_pend; (void)r_card; (void)r_ver;
+    uint32_t r_fwd = 0;  // the committed row's intersection with the next element (pipe_fwd), in the row's lane
+    uint32_t st_fwd = 0;
+    (void)r_link; (void)r_n; (void)r_ts; (void)r_clen; (void)r_pend; (void)r_card; (void)r_ver; (void)r_fwd; (void)st_fwd;
     uint32_t budget = (1u << PNP) - 1;
     bool ok = depth >= 2 && depth - 2 <= (uint32_t)PZ;
     bool needml = false;
@@ -1321,7 +1334,7 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
             const uint32_t pop = stampw >> 16;
             uint32_t j, it;
             if (pzero) { j = 0; it = 0; }
-            else if constexpr (RV) pipe_choose_rv(L, p.pslot, plen, pop, xd, p.preP + pb * LANES4, r_card, r_ver, j, it, st_stale);
+            else if constexpr (RV) pipe_choose_rv(L, p.pslot, plen, pop, xd, p.preP + pb * LANES4, r_card, r_ver, r_fwd, issued + 1, j, it, st_stale, st_fwd);
             else pipe_choose<RPL>(L, p.pslot, p.pslot + p.p_card, plen, pop, xd, p.preP + pb * LANES4, p.pver, j, it, st_stale);
             uint32_t leaf, nP, ts;
             if constexpr (RV) {
@@ -1407,6 +1420,15 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
                     break;
                 }
             }
+            // The next element, if wave 2 has brought it in already (a look, not a wait; the stamp is read before the row it
+            // vouches for): its intersection with the row committed below is forwarded to its compare, see pipe_fwd.
+            uint32_t nstamp = 0, nxd = 0;
+            if constexpr (RV) {
+                if (!pzero) {
+                    nstamp = lds_ld(L, p.pst + (issued & ((uint32_t)K::PREW - 1u)) * 4);
+                    nxd = lds_ld(L, p.xq + (issued & (K::PW - 1)) * 256 + lane * 4);
+                }
+            }
             // ---- commit.  Zero levels: the element's bits into the bit-sliced deferred sums
             {
                 uint32_t carry = xd;
@@ -1490,7 +1512,16 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
             if (curx) track(tx, xtag, xts);
             else track(ty, ytag, yts);
             }
-            const uint32_t cardn = wsum32((uint32_t)__popc(cw));
+            uint32_t cardn;
+            if constexpr (RV) {
+                // the new row's popcount and its intersection with the next element in one reduction (both <= 2048)
+                const uint32_t two = wsum32(((uint32_t)__popc(cw) << 16) | (uint32_t)__popc(cw & nxd));
+                cardn = two >> 16;
+                const bool known = (uni(nstamp) & 0xFFFFu) == issued + 1;
+                r_fwd = known && lane == j ? pipe_fwd(issued + 1, two & 0xFFFFu) : 0u;
+            } else {
+                cardn = wsum32((uint32_t)__popc(cw));
+            }
             const size_t prow = (size_t)P * NG + j;
             // (the row's version is odd while it is being rewritten: wave 2 may be reading it)
             uint32_t pv;
@@ -1518,7 +1549,10 @@ __device__ __forceinline__ void pipe_router(LA unsigned char* L, TreeDev* T, lon
             e += 1;
             pph<PROF>(pr, 3);
         }
-        if constexpr (PROF) pr.ph[13] += st_stale;
+        if constexpr (PROF) {
+            pr.ph[13] += st_stale;
+            if (lane == 0) atomicAdd((unsigned long long*)&T->mlprof[6], (unsigned long long)st_fwd);
+        }
         // ---- end of the run: the ring drains, deferred state goes where the next reader expects it ---------------
         lds_st(L, p.ctl + PC_END * 4, 1u);
         {
@@ -2179,6 +2213,11 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
     PIPE_CBAR();
     lds_st(L, p.ctl + PC_LGO * 4, 1u);
     (void)tolerance;
+    // Nodes of one row per lane: row versions come from the job number - this wave is their only writer, and a version only has to
+    // be odd while the row is written and afterwards an even value the row has not had before in this run: 4 j + 2 for all rows
+    // after a slot fill by job j, 4 j + 4 for the row job j writes, the odd values below them meanwhile (a run takes < 2^PNP
+    // jobs; pipe_pre / pipe_choose compare 20 bits).  Read back from LDS, the old version was a round trip per element.
+    constexpr bool LVER = RPL == 1;
 #pragma unroll 1
     while (true) {
         // ---- the next routed element -----------------------------------------------------------------------
@@ -2225,7 +2264,8 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
             if (lane == 0) lds_st(L, p.pst + (16 + si) * 4, NONE);
 #pragma unroll
             for (int q = 0; q < RPL; ++q) {
-                fv[q] = lds_ld(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4) | 1u;
+                if constexpr (LVER) fv[q] = 4u * j + 1u;
+                else fv[q] = lds_ld(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4) | 1u;
                 lds_st(L, p.lver + si * LANES4 + ((uint32_t)q * 64 + lane) * 4, fv[q]);
             }
             PIPE_CBAR();
@@ -2560,7 +2600,9 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
         }
         if (accept) {
             const uint32_t cardn = wsum32((uint32_t)__popc(cw));
-            const uint32_t rv = uni(lds_ld(L, p.lver + si * LANES4 + jl * 4));
+            uint32_t rv;
+            if constexpr (LVER) rv = 4u * j + 2u;
+            else rv = uni(lds_ld(L, p.lver + si * LANES4 + jl * 4));
             if (lane == 0) lds_st(L, p.lver + si * LANES4 + jl * 4, rv + 1);
             PIPE_CBAR();
             *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4) = cw;
@@ -2601,7 +2643,9 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
             const uint32_t s = cI++;
             const uint32_t slotw = SLOT_LAZY8;  // no uint8 slot: one fingerprint's cluster features are its centroid row
             const size_t m = lm + len;
-            const uint32_t rv = uni(lds_ld(L, p.lver + si * LANES4 + len * 4));
+            uint32_t rv;
+            if constexpr (LVER) rv = 4u * j + 2u;
+            else rv = uni(lds_ld(L, p.lver + si * LANES4 + len * 4));
             if (lane == 0) lds_st(L, p.lver + si * LANES4 + len * 4, rv + 1);
             PIPE_CBAR();
             *(LA uint32_t*)(L + sb + __umul24(len, FRBS) + lane * 4) = xd;
