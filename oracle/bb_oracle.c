@@ -287,6 +287,8 @@ struct bbo_tree {
     /* bbo_tree_edge_counts: observed only, no decision reads them */
     uint64_t edge[4];
     uint64_t tie_depth[8]; /* edge[3] by the depth of the node searched (root = 1; the last entry takes 8 and deeper) */
+    /* bbo_tree_split_counts: observed only, no decision reads them */
+    uint64_t split[BBO_SPLIT_COUNTS];
 };
 
 static Sub* sub_new(const bbo_tree* t) {
@@ -500,8 +502,81 @@ static int sub_try_merge(bbo_tree* t, Sub* T, const Sub* S) {
     return 1;
 }
 
+/* What a split met on its edges (bbo_tree_split_counts).  Called after the rows have been handed out: `old` are the m rows
+ * in their order before the split, `cents` their centroids as they lay in the node, to1[i] where row i went, s1 / s2 the
+ * similarities to fp1 / fp2 the decision used.  Everything else is computed again from the rows: nothing is handed back. */
+static void observe_split(bbo_tree* t, Sub* const* old, const uint8_t* cents, int m, int64_t f1, int64_t f2, const uint8_t* to1,
+                          int internal, int is_root) {
+    uint64_t* c = t->split;
+    const int F = t->F, nbytes = t->nbytes;
+    c[0]++;
+    c[1] += (uint64_t)internal;
+    c[2] += (uint64_t)is_root;
+    /* the majority vote: a column with 2 * count == m */
+    uint8_t* cen = (uint8_t*)calloc((size_t)nbytes, 1);
+    int tie_col = 0;
+    for (int j = 0; j < F; ++j) {
+        int cnt = 0;
+        for (int i = 0; i < m; ++i) cnt += (cents[(size_t)i * nbytes + (j >> 3)] >> (7 - (j & 7))) & 1;
+        if (2 * cnt == m) tie_col = 1;
+        if (m <= 1 ? cnt != 0 : 2 * cnt >= m) cen[j >> 3] |= (uint8_t)(0x80u >> (j & 7));
+    }
+    c[3] += (uint64_t)tie_col;
+    /* the two argmin steps: is the minimum attained by more than one row? */
+    uint32_t* card = (uint32_t*)malloc((size_t)m * sizeof(uint32_t));
+    double* sc = (double*)malloc((size_t)m * sizeof(double));
+    uint32_t *i1 = (uint32_t*)malloc((size_t)m * 4), *u1 = (uint32_t*)malloc((size_t)m * 4);
+    uint32_t *i2 = (uint32_t*)malloc((size_t)m * 4), *u2 = (uint32_t*)malloc((size_t)m * 4);
+    bbo_popcount_rows(cents, m, nbytes, card);
+    bbo_jt_arr_vec(cents, m, nbytes, cen, card, sc, NULL, NULL);
+    bbo_jt_arr_vec(cents, m, nbytes, cents + (size_t)f1 * nbytes, card, NULL, i1, u1);
+    bbo_jt_arr_vec(cents, m, nbytes, cents + (size_t)f2 * nbytes, card, NULL, i2, u2);
+    int at_min1 = 0, at_min2 = 0, equal_row = 0, equal_differ = 0, zero_row = 0;
+    for (int i = 0; i < m; ++i) {
+        at_min1 += sc[i] == sc[f1];
+        at_min2 += t->s1[i] == t->s1[f2];
+        if (i != (int)f1 && t->s1[i] == t->s2[i]) {
+            equal_row = 1;
+            if (i1[i] != i2[i] || u1[i] != u2[i]) equal_differ = 1;
+        }
+        zero_row |= card[i] == 0;
+    }
+    c[4] += (uint64_t)(at_min1 > 1);
+    c[5] += (uint64_t)(at_min2 > 1);
+    c[6] += (uint64_t)equal_row;
+    c[7] += (uint64_t)equal_differ;
+    c[8] += (uint64_t)(f1 == f2);
+    int n1 = 0;
+    for (int i = 0; i < m; ++i) n1 += to1[i];
+    const int n2 = m - n1;
+    c[9] += (uint64_t)(n1 == n2);
+    c[10] += (uint64_t)(n1 > n2);
+    /* the smaller half, as the engine picks it: node1's rows when n1 <= n2 */
+    const int small1 = n1 <= n2, s = small1 ? n1 : n2;
+    int over255 = 0, over65535 = 0, ones = 0, more = 0;
+    for (int i = 0; i < m; ++i) {
+        if ((to1[i] != 0) != small1) continue;
+        over255 |= old[i]->n > 255;
+        over65535 |= old[i]->n > 65535;
+        ones += old[i]->n == 1;
+        more += old[i]->n > 1;
+    }
+    c[11] += (uint64_t)over255;
+    c[12] += (uint64_t)over65535;
+    c[13] += (uint64_t)(s % 16 == 0);
+    c[14] += (uint64_t)(s % 16 == 1);
+    c[15] += (uint64_t)zero_row;
+    c[16] += (uint64_t)(ones == s);
+    c[17] += (uint64_t)(!over255 && ones > 0 && more > 0);
+    c[18] += (uint64_t)(s > 16);
+    c[19] += (uint64_t)(m > 124);
+    c[20] += (uint64_t)(f1 == 0);
+    c[21] += (uint64_t)(f1 == m - 1);
+    free(cen); free(card); free(sc); free(i1); free(u1); free(i2); free(u2);
+}
+
 /* _split_node, bitbirch.py:162-211 */
-static void split_node(bbo_tree* t, Node* node, Sub** outA, Sub** outB) {
+static void split_node(bbo_tree* t, Node* node, Sub** outA, Sub** outB, int is_root) {
     Sub* A = sub_new(t);
     Sub* B = sub_new(t);
     Node* node1 = node_new(t);
@@ -522,9 +597,14 @@ static void split_node(bbo_tree* t, Node* node, Sub** outA, Sub** outB) {
     bbo_most_dissimilar(node->cents, m, t->nbytes, t->F, &f1, &f2, t->s1, t->s2);
     Sub** old = (Sub**)malloc((size_t)m * sizeof(Sub*));
     memcpy(old, node->subs, (size_t)m * sizeof(Sub*));
+    /* (for observe_split only: the rows as they lay, and where each went) */
+    uint8_t* seen_cents = (uint8_t*)malloc((size_t)m * (size_t)t->nbytes);
+    uint8_t* seen_to1 = (uint8_t*)malloc((size_t)m);
+    memcpy(seen_cents, node->cents, (size_t)m * (size_t)t->nbytes);
     node->len = 0;
     for (int i = 0; i < m; ++i) {
         int to1 = (t->s1[i] > t->s2[i]) || (i == (int)f1); /* bitbirch.py:193-200 */
+        seen_to1[i] = (uint8_t)to1;
         if (to1) {
             node_append(t, node1, old[i]);
             sub_add(t, A, old[i]);
@@ -537,6 +617,9 @@ static void split_node(bbo_tree* t, Node* node, Sub** outA, Sub** outB) {
      * final value is observable */
     sub_recompute_centroid(t, A);
     sub_recompute_centroid(t, B);
+    observe_split(t, old, seen_cents, m, f1, f2, seen_to1, !node->is_leaf, is_root);
+    free(seen_cents);
+    free(seen_to1);
     free(old);
     t->stats[4]++;
     t->stats[5]++;
@@ -601,7 +684,7 @@ static int node_insert(bbo_tree* t, Node* node, Sub* S, int depth) {
     }
     if (node_insert(t, T->child, S, depth + 1)) {
         Sub *A, *B;
-        split_node(t, T->child, &A, &B);
+        split_node(t, T->child, &A, &B, 0);
         /* update_split_subclusters, bitbirch.py:289-303 */
         node_set_row(t, node, best, A);
         node_append(t, node, B);
@@ -626,7 +709,7 @@ static void tree_insert(bbo_tree* t, Sub* S) {
     if (!t->root) tree_init_root(t);
     if (node_insert(t, t->root, S, 1)) { /* bitbirch.py:778-782 */
         Sub *A, *B;
-        split_node(t, t->root, &A, &B);
+        split_node(t, t->root, &A, &B, 1);
         Node* nr = node_new(t);
         t->stats[5]++;
         node_append(t, nr, A);
@@ -683,6 +766,7 @@ void bbo_tree_reset(bbo_tree* t) {
     memset(t->stats, 0, sizeof(t->stats)); /* the counters restart with the tree, as the engine's do */
     memset(t->edge, 0, sizeof(t->edge));
     memset(t->tie_depth, 0, sizeof(t->tie_depth));
+    memset(t->split, 0, sizeof(t->split));
 }
 
 void bbo_tree_destroy(bbo_tree* t) {
@@ -826,3 +910,77 @@ void bbo_tree_stats(const bbo_tree* t, uint64_t* out7) { memcpy(out7, t->stats, 
 void bbo_tree_edge_counts(const bbo_tree* t, uint64_t* out4) { memcpy(out4, t->edge, sizeof(t->edge)); }
 
 void bbo_tree_tie_depths(const bbo_tree* t, uint64_t* out8) { memcpy(out8, t->tie_depth, sizeof(t->tie_depth)); }
+
+void bbo_tree_split_counts(const bbo_tree* t, uint64_t* out) { memcpy(out, t->split, sizeof(t->split)); }
+
+/* the leaf chain as an array: chain[p] = the leaf node at position p */
+static int64_t chain_nodes(const bbo_tree* t, const Node** chain) {
+    int64_t k = 0;
+    for (const Node* nd = t->first_leaf; nd; nd = nd->next_leaf, ++k)
+        if (chain) chain[k] = nd;
+    return k;
+}
+
+typedef struct Walk {
+    const bbo_tree* t;
+    const Node** chain;
+    int64_t n_chain, nodes, rows;
+    int32_t* node_out;
+    uint64_t* row_n;
+    uint32_t *row_id, *row_pop;
+    uint8_t* row_cent;
+    uint64_t* row_ls;
+} Walk;
+
+static void walk_node(Walk* w, const Node* nd, int depth) {
+    const bbo_tree* t = w->t;
+    if (w->node_out) {
+        int64_t pos = -1;
+        if (nd->is_leaf)
+            for (int64_t p = 0; p < w->n_chain; ++p)
+                if (w->chain[p] == nd) { pos = p; break; }
+        int32_t* o = w->node_out + 4 * w->nodes;
+        o[0] = depth;
+        o[1] = nd->is_leaf;
+        o[2] = nd->len;
+        o[3] = (int32_t)pos;
+    }
+    w->nodes++;
+    for (int i = 0; i < nd->len; ++i) {
+        const Sub* s = nd->subs[i];
+        const int64_t r = w->rows++;
+        if (w->row_n) w->row_n[r] = s->n;
+        if (w->row_id) w->row_id[r] = s->id;
+        /* the node's own copy of the row and its popcount: what the next search of this node compares with */
+        if (w->row_pop) w->row_pop[r] = nd->cards[i];
+        if (w->row_cent) memcpy(w->row_cent + (size_t)r * t->nbytes, nd->cents + (size_t)i * t->nbytes, (size_t)t->nbytes);
+        if (w->row_ls)
+            for (int j = 0; j < t->F; ++j) w->row_ls[(size_t)r * t->F + j] = sub_ls(s, j);
+    }
+    for (int i = 0; i < nd->len; ++i)
+        if (nd->subs[i]->child) walk_node(w, nd->subs[i]->child, depth + 1);
+}
+
+void bbo_tree_walk(const bbo_tree* t, int64_t* n_nodes, int64_t* n_rows, int32_t* nodes, uint64_t* row_n, uint32_t* row_id,
+                   uint32_t* row_popcount, uint8_t* row_centroids, uint64_t* row_linear_sums) {
+    Walk w;
+    memset(&w, 0, sizeof(w));
+    w.t = t;
+    if (t->root) {
+        if (nodes) {
+            w.n_chain = chain_nodes(t, NULL);
+            w.chain = (const Node**)malloc((size_t)(w.n_chain > 0 ? w.n_chain : 1) * sizeof(*w.chain));
+            chain_nodes(t, w.chain);
+        }
+        w.node_out = nodes;
+        w.row_n = row_n;
+        w.row_id = row_id;
+        w.row_pop = row_popcount;
+        w.row_cent = row_centroids;
+        w.row_ls = row_linear_sums;
+        walk_node(&w, t->root, 1);
+        free((void*)w.chain);
+    }
+    if (n_nodes) *n_nodes = w.nodes;
+    if (n_rows) *n_rows = w.rows;
+}

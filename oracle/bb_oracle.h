@@ -110,6 +110,29 @@ void bbo_tree_edge_counts(const bbo_tree* t, uint64_t* out4);
 /* [3] of the edge counts by the depth of the node that was searched: out8[d - 1] for depth d (the root is 1), the last
  * entry for 8 and deeper.  Depths below the tree's deepest are internal levels. */
 void bbo_tree_tie_depths(const bbo_tree* t, uint64_t* out8);
+/* what the node splits (_split_node, bitbirch.py:162-211, with jt_most_dissimilar_packed, similarity.cpp:413-471) met on
+ * their edges, since create or reset; no decision reads them.  Splits ...
+ * [0] in all, [1] of internal nodes, [2] of the root,
+ * [3] with a column whose count c over the node's m centroids has 2 * c == m (the majority vote's tie),
+ * [4] whose first argmin (similarity to the majority centroid) is attained by more than one row, [5] the same for the second
+ *     argmin (similarity to fp1),
+ * [6] with a row other than fp1 whose similarities to fp1 and to fp2 are equal, [7] with such a row whose two
+ *     (intersection, union) pairs differ,
+ * [8] with fp1 == fp2, [9] with n1 == n2, [10] with n1 > n2 (n1: rows that went to the new node, n2: rows that stayed),
+ * and, of the SMALLER half (the new node's rows when n1 <= n2, else the rows that stayed; s rows):
+ * [11] with a row of n_samples > 255, [12] of n_samples > 65 535, [13] with s % 16 == 0, [14] with s % 16 == 1,
+ * [16] all of whose rows have n_samples == 1, [17] whose rows all have n_samples <= 255, some == 1 and some > 1, [18] s > 16;
+ * [15] with a row of popcount zero in the node, [19] of a node of more than 124 rows, [20] whose fp1 is row 0, [21] whose fp1
+ * is the last row.  [22..23] are zero. */
+#define BBO_SPLIT_COUNTS 24
+void bbo_tree_split_counts(const bbo_tree* t, uint64_t* out24);
+/* The whole tree in pre-order: the root first, then the subtrees of its rows in row order.  Call it with NULL arrays for the
+ * counts, then with arrays of that size; any array may be NULL.
+ * nodes: n_nodes x 4 int32 [depth (the root is 1), leaf flag, length, position in the leaf chain (-1: an internal node)];
+ * per row, the rows of node k after those of node k - 1: n_samples, BitFeature id (0xFFFFFFFF: a tracking row), popcount
+ * and packed centroid as the node holds them, linear sum (n_features uint64). */
+void bbo_tree_walk(const bbo_tree* t, int64_t* n_nodes, int64_t* n_rows, int32_t* nodes, uint64_t* row_n, uint32_t* row_id,
+                   uint32_t* row_popcount, uint8_t* row_centroids, uint64_t* row_linear_sums);
 
 #ifdef __cplusplus
 }

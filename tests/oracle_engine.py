@@ -11,6 +11,10 @@ import numpy as np
 REPO = Path(__file__).resolve().parents[1]
 _LIB = None
 _W = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+# bbo_tree_split_counts, in its order ("small": of the smaller half, the one the engine sums)
+SPLIT_COUNTS = ("splits", "internal", "root", "majority_tie", "argmin1_tie", "argmin2_tie", "equal_sims", "equal_sims_pairs_differ",
+                "fp1_is_fp2", "n1_eq_n2", "n1_gt_n2", "small_over_255", "small_over_65535", "small_mod16_0", "small_mod16_1", "zero_row",
+                "small_all_single", "small_u8_with_single", "small_over_16", "m_over_124", "fp1_row0", "fp1_last_row", "_22", "_23")
 
 
 def oracle_lib() -> C.CDLL:
@@ -47,6 +51,8 @@ def oracle_lib() -> C.CDLL:
         "bbo_tree_stats": (None, [vp, vp]),
         "bbo_tree_edge_counts": (None, [vp, vp]),
         "bbo_tree_tie_depths": (None, [vp, vp]),
+        "bbo_tree_split_counts": (None, [vp, vp]),
+        "bbo_tree_walk": (None, [vp, C.POINTER(i64), C.POINTER(i64), vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         fn = getattr(lib, name)
@@ -133,6 +139,25 @@ class OracleEngine:
         out = np.zeros(8, dtype=np.uint64)
         self.lib.bbo_tree_tie_depths(self._h, out.ctypes.data)
         return [int(v) for v in out]
+
+    def split_counts(self):
+        r"""name -> how many node splits met that condition since create or reset (SPLIT_COUNTS, bb_oracle.h)."""
+        out = np.zeros(24, dtype=np.uint64)
+        self.lib.bbo_tree_split_counts(self._h, out.ctypes.data)
+        return {name: int(v) for name, v in zip(SPLIT_COUNTS, out)}
+
+    def walk(self):
+        r"""The whole tree in pre-order (the root first, then the subtrees of its rows in row order), as
+        tree_image_format.Image.walk gives it: nodes (n, 4) int32 [depth, leaf flag, length, position in the leaf chain or
+        -1], and per row n, id, pop, cent, ls."""
+        n_nodes, n_rows = C.c_int64(-1), C.c_int64(-1)
+        self.lib.bbo_tree_walk(self._h, C.byref(n_nodes), C.byref(n_rows), None, None, None, None, None, None)
+        k, r = n_nodes.value, n_rows.value
+        w = dict(nodes=np.empty((k, 4), np.int32), n=np.empty(r, np.uint64), id=np.empty(r, np.uint32), pop=np.empty(r, np.uint32),
+                 cent=np.empty((r, self.nbytes), np.uint8), ls=np.empty((r, self.n_features), np.uint64))
+        self.lib.bbo_tree_walk(self._h, C.byref(n_nodes), C.byref(n_rows), *[w[key].ctypes.data for key in ("nodes", "n", "id", "pop", "cent", "ls")])
+        assert (n_nodes.value, n_rows.value) == (k, r)
+        return w
 
     def close(self):
         if self._h:

@@ -13,6 +13,7 @@ import functools
 import os
 import subprocess
 import sys
+import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -171,6 +172,16 @@ class Raw:
         out = np.zeros(8, np.uint64)
         ok(self.lib, self.lib.bbh_tree_kernel_counts(self.h, at(out)))
         return [int(v) for v in out]
+
+    def save_image(self) -> bytes:
+        r"""The tree's image (bbh_tree_save_fd into a temporary file); the tree stays as it was."""
+        with tempfile.TemporaryFile() as f:
+            written = C.c_uint64(0)
+            ok(self.lib, self.lib.bbh_tree_save_fd(self.h, f.fileno(), 0, C.byref(written)))
+            f.seek(0)
+            image = f.read()
+        assert len(image) == written.value, (len(image), written.value)
+        return image
 
 
 @functools.lru_cache(maxsize=None)

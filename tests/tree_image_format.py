@@ -76,6 +76,70 @@ class Image:
         at, m, i = self._group(ib + row // NG)
         return at + m * 32 + (i * NG + row % NG) * 32
 
+    def card_at(self, ib: int, row: int) -> int:
+        at, m, i = self._group(ib + row // NG)
+        return at + m * 160 + (i * NG + row % NG) * 4
+
+    def cent_at(self, ib: int, row: int) -> int:
+        at, m, i = self._group(ib + row // NG)
+        return at + m * 176 + (i * NG + row % NG) * self.rb
+
+    def row(self, ib: int, row: int) -> dict:
+        r"""The row record of row `row` of the node that starts at block `ib`: BitFeature id, n_samples, slot word."""
+        sub, n, slot = struct.unpack_from("<3I", self.buf, self.rm_at(ib, row))
+        return dict(sub=sub, n=n, tier=slot >> 30, slot=slot & 0x3FFFFFFF)
+
+    def linear_sum(self, leaf: bool, rec: dict, cent: np.ndarray) -> np.ndarray:
+        r"""The linear sum (F uint64) of a row: a leaf row of one member keeps it in its centroid row, every other row in the
+        cluster-feature section its slot word names (tier 0 / 1 / 2: cf8 / cf16 / cf32); tracking rows are always cf32."""
+        F = self.h["F"]
+        if leaf and rec["n"] == 1:
+            return np.unpackbits(cent)[:F].astype(np.uint64)
+        assert rec["tier"] == 2 if not leaf else rec["tier"] in (0, 1, 2), ("tier", leaf, rec)
+        width = 1 << rec["tier"]
+        assert rec["slot"] < (self.h["n8"], self.h["n16"], self.h["n32"])[rec["tier"]], ("slot beyond its section", rec)
+        at = self.sections[2 + rec["tier"]] + rec["slot"] * F * width
+        return np.frombuffer(self.buf, dtype=("<u1", "<u2", "<u4")[rec["tier"]], count=F, offset=at).astype(np.uint64)
+
+    def walk(self) -> dict:
+        r"""The whole tree in pre-order - the root (ctr[C_ROOT]) first, then the subtrees of its rows in row order, by their
+        link words - in the shape of OracleEngine.walk: nodes (n, 4) int32 [depth (the root is 1), leaf flag, length,
+        position in the leaf chain from ctr[C_FIRST_LEAF] or -1], and per row (node after node) n, id, pop, cent, ls."""
+        F, nb = self.h["F"], self.h["F"] // 8
+        if self.T == 0:
+            return dict(nodes=np.empty((0, 4), np.int32), n=np.empty(0, np.uint64), id=np.empty(0, np.uint32), pop=np.empty(0, np.uint32),
+                        cent=np.empty((0, nb), np.uint8), ls=np.empty((0, F), np.uint64))
+        pos, b, before = {}, self.h["ctr"][C_FIRST_LEAF], NONE
+        while b != NONE:
+            assert b not in pos and b < self.T, "the leaf chain loops or leaves the image"
+            assert self.node(b)["prev"] == before, f"leaf {b} at chain position {len(pos)}: prev is {self.node(b)['prev']}, the leaf before it is {before}"
+            pos[b] = len(pos)
+            before, b = b, self.node(b)["next"]
+        nodes, ns, ids, pops, cents, lss = [], [], [], [], [], []
+        seen = set()
+
+        def visit(ib, depth):
+            assert ib < self.T and ib not in seen, ("link word", ib)
+            seen.add(ib)
+            nd = self.node(ib)
+            assert nd["cap"] >= nd["len"], ("node header", ib, nd)
+            nodes.append([depth, nd["leaf"], nd["len"], pos.get(ib, -1) if nd["leaf"] else -1])
+            for r in range(nd["len"]):
+                rec = self.row(ib, r)
+                cent = np.frombuffer(self.buf, np.uint8, count=nb, offset=self.cent_at(ib, r))
+                ns.append(rec["n"])
+                ids.append(rec["sub"])
+                pops.append(self.u32(self.card_at(ib, r)))
+                cents.append(cent)
+                lss.append(self.linear_sum(bool(nd["leaf"]), rec, cent))
+            if not nd["leaf"]:
+                for r in range(nd["len"]):
+                    visit(self.u32(self.link_at(ib, r)), depth + 1)
+
+        visit(self.h["ctr"][C_ROOT], 1)
+        return dict(nodes=np.array(nodes, np.int32).reshape(-1, 4), n=np.array(ns, np.uint64), id=np.array(ids, np.uint32),
+                    pop=np.array(pops, np.uint32), cent=np.array(cents, np.uint8).reshape(-1, nb), ls=np.array(lss, np.uint64).reshape(-1, F))
+
     def u32(self, at: int) -> int:
         return struct.unpack_from("<I", self.buf, at)[0]
 
@@ -88,6 +152,123 @@ class Image:
 
     def live_nodes(self) -> list[int]:
         return [b for b in range(self.T) if self.node(b)["cap"]]
+
+
+def walk_children(walk: dict):
+    r"""-> (row_start, children): the first row of every node of a walk, and children[k] = the nodes its rows link to (in row
+    order; empty for a leaf), from the pre-order alone."""
+    nodes = walk["nodes"]
+    row_start = np.concatenate([[0], np.cumsum(nodes[:, 2])]).astype(np.int64)
+    children = [[] for _ in range(len(nodes))]
+    at = 0
+
+    def parse():
+        nonlocal at
+        k = at
+        assert k < len(nodes), "the pre-order ends inside a node's subtrees"
+        at += 1
+        if not nodes[k, 1]:
+            for _ in range(int(nodes[k, 2])):
+                c = at
+                assert c < len(nodes) and nodes[c, 0] == nodes[k, 0] + 1, f"node {k}: a child is missing or on the wrong level"
+                children[k].append(c)
+                parse()
+        return k
+
+    if len(nodes):
+        parse()
+    assert at == len(nodes), "nodes beyond the root's subtrees"
+    return row_start, children
+
+
+def walk_faults(walk: dict) -> list[str]:
+    r"""What every tree must satisfy, checked on a walk whatever produced it; -> the broken invariants, in words.
+    - a tracking row's n_samples and linear sum are the sums over the rows of the node it links to, its id is 0xFFFFFFFF;
+    - every row's centroid is bit j = (2 * ls[j] >= n) (n <= 1: ls[j] != 0) and its popcount is that centroid's;
+    - leaf rows carry distinct ids; all leaves are on the deepest level;
+    - the leaf chain visits every leaf exactly once (positions 0 .. leaves - 1), internal nodes are not on it."""
+    faults = []
+    nodes = walk["nodes"]
+    if len(nodes) == 0:
+        return faults
+    try:
+        row_start, children = walk_children(walk)
+    except AssertionError as e:
+        return [f"structure: {e}"]
+    F = walk["ls"].shape[1]
+    n, ls = walk["n"], walk["ls"]
+    want = np.where((n <= 1)[:, None], ls != 0, 2 * ls >= n[:, None])
+    got = np.unpackbits(walk["cent"], axis=1)[:, :F].astype(bool)
+    row_node = np.repeat(np.arange(len(nodes)), nodes[:, 2])
+    for r in np.flatnonzero((want != got).any(axis=1))[:5]:
+        faults.append(f"row {r - row_start[row_node[r]]} of node {row_node[r]} (n {n[r]}): the centroid is not the majority of its linear sum, "
+                      f"first at feature {int(np.argmax(want[r] != got[r]))}")
+    if np.unpackbits(walk["cent"], axis=1)[:, F:].any():
+        faults.append("a centroid row has bits beyond n_features")
+    for r in np.flatnonzero(got.sum(axis=1) != walk["pop"])[:5]:
+        faults.append(f"row {r - row_start[row_node[r]]} of node {row_node[r]}: popcount {walk['pop'][r]}, its centroid has {int(got[r].sum())}")
+    for k in range(len(nodes)):
+        lo, hi = row_start[k], row_start[k + 1]
+        if nodes[k, 1]:
+            if (walk["id"][lo:hi] == NONE).any():
+                faults.append(f"leaf {k}: a row without an id")
+            continue
+        if (walk["id"][lo:hi] != NONE).any():
+            faults.append(f"internal node {k}: a tracking row with an id")
+        for j, c in enumerate(children[k]):
+            clo, chi = row_start[c], row_start[c + 1]
+            if int(n[lo + j]) != int(n[clo:chi].sum()):
+                faults.append(f"row {j} of node {k}: n_samples {n[lo + j]}, its child's rows add up to {int(n[clo:chi].sum())}")
+            d = ls[lo + j] != ls[clo:chi].sum(axis=0)
+            if d.any():
+                f = int(np.argmax(d))
+                faults.append(f"row {j} of node {k}: linear sum differs from the sum over its child's rows in {int(d.sum())} features, first {f}: "
+                              f"{ls[lo + j, f]} against {int(ls[clo:chi, f].sum())}")
+    leaf_ids = walk["id"][np.repeat(nodes[:, 1] != 0, nodes[:, 2])]
+    if len(set(leaf_ids.tolist())) != leaf_ids.size:
+        faults.append("two leaf rows share an id")
+    leaves = nodes[nodes[:, 1] != 0]
+    if (leaves[:, 0] != nodes[:, 0].max()).any():
+        faults.append("a leaf above the deepest level")
+    if sorted(leaves[:, 3].tolist()) != list(range(len(leaves))):
+        faults.append(f"the leaf chain does not visit every leaf exactly once: positions {sorted(leaves[:, 3].tolist())[:8]}... of {len(leaves)} leaves")
+    if (nodes[nodes[:, 1] == 0][:, 3] != -1).any():
+        faults.append("an internal node with a chain position")
+    return faults
+
+
+def check_walk(walk: dict, who: str) -> None:
+    faults = walk_faults(walk)
+    assert not faults, f"{who}: " + "; ".join(faults[:6])
+
+
+def same_walk(got: dict, want: dict, who: str = "image against oracle") -> None:
+    r"""Two walks are equal, exactly: structure, lengths, chain positions and every row's n_samples, id, popcount, centroid and
+    linear sum; the message names the first node and row that differ."""
+    assert got["nodes"].shape == want["nodes"].shape and (got["nodes"] == want["nodes"]).all(), \
+        f"{who}: tree structure [depth, leaf, length, chain position] differs, first at node " \
+        f"{int(np.argmax((got['nodes'] != want['nodes']).any(axis=1))) if got['nodes'].shape == want['nodes'].shape else (got['nodes'].shape, want['nodes'].shape)}"
+    row_node = np.repeat(np.arange(len(want["nodes"])), want["nodes"][:, 2])
+    row_start = np.concatenate([[0], np.cumsum(want["nodes"][:, 2])])
+    for key in ("n", "id", "pop", "cent", "ls"):
+        a, b = got[key], want[key]
+        assert a.shape == b.shape, (who, key, a.shape, b.shape)
+        d = (a != b) if a.ndim == 1 else (a != b).any(axis=1)
+        if d.any():
+            r = int(np.argmax(d))
+            k = int(row_node[r])
+            kind = "leaf" if want["nodes"][k, 1] else "internal node"
+            detail = f"{a[r]} against {b[r]}" if a.ndim == 1 else f"{int((a[r] != b[r]).sum())} entries, first {int(np.argmax(a[r] != b[r]))}: {a[r][np.argmax(a[r] != b[r])]} against {b[r][np.argmax(a[r] != b[r])]}"
+            raise AssertionError(f"{who}: `{key}` differs in {int(d.sum())} rows, first row {r - row_start[k]} of node {k} ({kind}, depth {want['nodes'][k, 0]}): {detail}")
+
+
+def walk_leaves(walk: dict) -> dict:
+    r"""The leaf rows of a walk in chain order: what bbh_tree_export_leaves / bbo_tree_export_leaves give."""
+    nodes = walk["nodes"]
+    row_start = np.concatenate([[0], np.cumsum(nodes[:, 2])]).astype(np.int64)
+    order = sorted((int(nodes[k, 3]), k) for k in range(len(nodes)) if nodes[k, 1])
+    rows = np.concatenate([np.arange(row_start[k], row_start[k + 1]) for _, k in order]) if order else np.empty(0, np.int64)
+    return dict(ids=walk["id"][rows], ns=walk["n"][rows], cents=walk["cent"][rows], ls=walk["ls"][rows])
 
 
 def synthetic_image(n_features: int = 64, bf: int = 5) -> bytes:
