@@ -137,6 +137,8 @@ struct TreeDev {
     unsigned long long mlprof[8];  // multi-level router (phase-timer build): tracking-CF cache misses, levels committed; [6]: forwarded
                                    // intersections the single-level router consumed (pipe_fwd)
     unsigned long long rprof[4];   // router (phase-timer build): cycles waiting for a ring entry / wave 2's stamp / a leaf's pending jobs / a full leaf's decision
+    unsigned long long lprof[8];   // leaf engine (phase-timer build): jobs on a singleton / with cached / loaded uint8 cluster features / wide tier,
+                                   // cycles waiting for the loaded ones
     // job of the next launch
     const uint8_t* rows;
     long long row_stride;
@@ -2796,6 +2798,7 @@ int init_empty(bbh_tree* t) {
     std::memset(h.splitprof, 0, sizeof(h.splitprof));
     std::memset(h.mlprof, 0, sizeof(h.mlprof));
     std::memset(h.rprof, 0, sizeof(h.rprof));
+    std::memset(h.lprof, 0, sizeof(h.lprof));
     h.stats[5] = 1;
     t->chain_valid = false;
     t->pipe_ml = false;
@@ -2992,7 +2995,14 @@ static void print_pipe_phases(const bbh_tree* t) {
     for (int i = 0; i < 3; ++i)
         fprintf(stderr, " %s: %.3f/insert x %.0f cycles", kd[i], n > 0 ? (double)t->h.sphase[2 * i + 1] / n : 0.0,
                 t->h.sphase[2 * i + 1] ? (double)t->h.sphase[2 * i] / (double)t->h.sphase[2 * i + 1] : 0.0);
-    fprintf(stderr, "\n");
+    {
+        // (on the same line: the launch-trace tests pin the list of report lines)
+        const unsigned long long* lp = t->h.lprof;
+        fprintf(stderr, "; cluster features, per insert: singleton target %.4f, uint8 from the LDS cache %.4f, uint8 from HBM %.4f, wide tier %.4f, "
+                "waiting for the HBM load %.0f cycles/insert (%.0f per load)\n",
+                n > 0 ? (double)lp[0] / n : 0.0, n > 0 ? (double)lp[1] / n : 0.0, n > 0 ? (double)lp[2] / n : 0.0, n > 0 ? (double)lp[3] / n : 0.0,
+                n > 0 ? (double)lp[4] / n : 0.0, lp[2] ? (double)lp[4] / (double)lp[2] : 0.0);
+    }
     fprintf(stderr, "[bbhip pipe router waits, per insert] ring entry %.0f, row + pre-compare of wave 2 %.0f, pending jobs of a nearly full leaf %.0f, "
             "decision on a full leaf %.0f\n", n > 0 ? (double)t->h.rprof[0] / n : 0.0, n > 0 ? (double)t->h.rprof[1] / n : 0.0,
             n > 0 ? (double)t->h.rprof[2] / n : 0.0, n > 0 ? (double)t->h.rprof[3] / n : 0.0);
@@ -3301,6 +3311,7 @@ int run_insert_multi(std::vector<Job>& jobs, hipStream_t s) {
             std::memcpy(h.splitprof, back.splitprof, sizeof(h.splitprof));
             std::memcpy(h.mlprof, back.mlprof, sizeof(h.mlprof));
             std::memcpy(h.rprof, back.rprof, sizeof(h.rprof));
+            std::memcpy(h.lprof, back.lprof, sizeof(h.lprof));
             j.done += back.processed;
             t->kcount[label.kcol] += (uint64_t)back.processed;
             t->kcount[3 + label.kcol] += 1;

@@ -173,6 +173,8 @@ static_assert(pipe_layout(50, 1).leaf0 == pipe_layout(50).leaf0 && pipe_layout(5
 
 #if defined(__HIPCC__)
 
+#include "bb_pipe_bytes.h"
+
 #define PIPE_SPIN_LIMIT (1u << 22)
 // Where a bounded wait of a launch gave up: the abort flag itself carries the line of this file (any non-zero value aborts),
 // the workgroup's thread 0 hands it to the host with STOP_INTERNAL (TreeDev::giveup_line).  Round 4 recorded it with an
@@ -2201,6 +2203,13 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
     (void)det;
     constexpr bool shared = SH;
     static_assert(!SH || RPL > 1, "sharing is for nodes of several rows per lane");
+    // nodes of one row per lane behind the single-level router, where this wave is the longest chain: the control block in one
+    // read per poll, the packed merge path four bytes at a time (see the head of the loop body / the packed merge path)
+    constexpr bool BYTES4 = RPL == 1 && !K::ML, POLL4 = RPL == 1 && !K::ML;
+    // (phase-timer builds) jobs by kind - singleton target, uint8 cluster features from the LDS cache, from HBM, wide tier - and the
+    // cycles between the issue of the HBM load and its data
+    u64 lp[5] = {0, 0, 0, 0, 0};
+    (void)lp;
     constexpr uint32_t LANES4 = (uint32_t)RPL * 256;
     // row versions, published slot tags / lengths and stamps start from zero, then wave 3 may go
 #pragma unroll
@@ -2225,16 +2234,26 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
             uint32_t spins = 0;
             bool stop = false;
             while (true) {
-                const uint32_t h = uni(lds_ld(L, p.ctl + PC_HEAD * 4));
+                uint32_t h, c_end = 0, c_abort = 0;
+                if constexpr (POLL4) {
+                    // {head, tail, end, abort} in one read, as the router's loop top does (three dependent reads before)
+                    const u32x4_t c4 = lds_ld4(L, p.ctl);
+                    h = uni(c4.x); c_end = uni(c4.z); c_abort = uni(c4.w);
+                } else {
+                    h = uni(lds_ld(L, p.ctl + PC_HEAD * 4));
+                }
                 if (h != j) {
                     PIPE_CBAR();
                     break;
                 }
-                if (uni(lds_ld(L, p.ctl + PC_END * 4)) != 0u) {
+                if constexpr (!POLL4) c_end = uni(lds_ld(L, p.ctl + PC_END * 4));
+                if (c_end != 0u) {
+                    // (the head is written before the end flag: read again behind the flag, it is final)
                     if (uni(lds_ld(L, p.ctl + PC_HEAD * 4)) == j) { stop = true; break; }
                     continue;
                 }
-                if (uni(lds_ld(L, p.ctl + PC_ABORT * 4)) != 0u) { stop = true; break; }
+                if constexpr (!POLL4) c_abort = uni(lds_ld(L, p.ctl + PC_ABORT * 4));
+                if (c_abort != 0u) { stop = true; break; }
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > PIPE_SPIN_LIMIT) { (PIPE_MARK(), lds_st(L, p.ctl + PC_ABORT * 4, (uint32_t)__LINE__)); stop = true; break; }
             }
@@ -2421,8 +2440,10 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
         // are spread to four bytes by one 24-bit multiply
         const uint32_t xr = __builtin_bitreverse32(xd);
         uint32_t xs[8];
+        if constexpr (!BYTES4) {  // (BYTES4: spread where the decision is known to need them, see below)
 #pragma unroll
-        for (int u = 0; u < 8; ++u) xs[u] = __umul24((xr >> (24 - 8 * (u >> 1) + 4 * (u & 1))) & 15u, 0x204081u) & 0x01010101u;
+            for (int u = 0; u < 8; ++u) xs[u] = __umul24((xr >> (24 - 8 * (u >> 1) + 4 * (u & 1))) & 15u, 0x204081u) & 0x01010101u;
+        }
         const bool packed = tierT == 0 && new_n <= 255;  // uint8 cluster features before and after: the common case
         const u64 s1n = s1T + pop;
         // merge_accept_fn on exact moments (_merges.py), float64 in the reference's operation order
@@ -2478,10 +2499,14 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
             if (nT == 1) {
                 // a singleton: its linear sum is its centroid (bitbirch.py:423-435; it has no uint8 slot yet, see SLOT_LAZY8),
                 // the dot product the intersection
-                const uint32_t cr = __builtin_bitreverse32(*(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4));
+                if constexpr (!BYTES4) {
+                    const uint32_t cr = __builtin_bitreverse32(*(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4));
 #pragma unroll
-                for (int u = 0; u < 8; ++u) w[u] = __umul24((cr >> (24 - 8 * (u >> 1) + 4 * (u & 1))) & 15u, 0x204081u) & 0x01010101u;
+                    for (int u = 0; u < 8; ++u) w[u] = __umul24((cr >> (24 - 8 * (u >> 1) + 4 * (u & 1))) & 15u, 0x204081u) & 0x01010101u;
+                }
+                // (BYTES4: the two rows are spread to bytes once the pair is accepted - a rejected pair never needs them)
                 dot = inter;
+                if constexpr (PROF) lp[0] += 1;
             } else {
                 if constexpr (NCF > 0) {
                     const u64 m = __ballot(lane < (uint32_t)NCF && ctagv == slotT);
@@ -2491,15 +2516,32 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
                 if (chit != NONE) {
                     q0 = *(LA u32x4_t*)(L + p.cfc + chit * 2048 + lane * 32);
                     q1 = *(LA u32x4_t*)(L + p.cfc + chit * 2048 + lane * 32 + 16);
+                    if constexpr (PROF) lp[1] += 1;
                 } else {
                     const size_t cfi = (size_t)slotT * 2048 + (size_t)lane * 32;
                     q0 = ldg<u32x4_t>(g_cf8 + cfi);
                     q1 = ldg<u32x4_t>(g_cf8 + cfi + 16);
+                    if constexpr (PROF) {
+                        // (every store of the jobs before was issued a compare ago: what is waited for here is this load)
+                        const u64 w0 = __builtin_amdgcn_s_memtime();
+                        asm volatile("s_waitcnt vmcnt(0)" : "+v"(q0), "+v"(q1) : : "memory");
+                        lp[4] += __builtin_amdgcn_s_memtime() - w0;
+                        lp[2] += 1;
+                    }
                 }
                 w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
                 uint32_t d32 = 0;
+                if constexpr (BYTES4) {
+                    // one 4 x u8 dot-accumulate per dword on the element's 0 / 1 bytes
 #pragma unroll
-                for (int u = 0; u < 8; ++u) d32 = __builtin_amdgcn_sad_u8(w[u] & ((xs[u] << 8) - xs[u]), 0u, d32);  // (0x01 -> 0xFF per byte)
+                    for (int u = 0; u < 8; ++u) {
+                        xs[u] = bbp_expand_dword(xr, u);
+                        d32 = __builtin_amdgcn_udot4(w[u], xs[u], d32, false);
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) d32 = __builtin_amdgcn_sad_u8(w[u] & ((xs[u] << 8) - xs[u]), 0u, d32);  // (0x01 -> 0xFF per byte)
+                }
                 dot = wsum32(d32);
             }
             pph<PROF>(pr, 8);
@@ -2511,9 +2553,22 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
                     // two members: a feature is in the centroid if either has it (2 ls >= 2), no majority vote to take;
                     // the BitFeature gets its uint8 row now (SLOT_LAZY8)
                     slotN = c8++;
+                    if constexpr (BYTES4) {
+                        const uint32_t cd = *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4);
+                        const uint32_t cr = __builtin_bitreverse32(cd);
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) w[u] = bbp_expand_dword(cr, u) + bbp_expand_dword(xr, u);
+                        cw = cd | xd;
+                    } else {
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) w[u] += xs[u];
+                        cw = *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4) | xd;
+                    }
+                } else if constexpr (BYTES4) {
+                    // the majority vote four bytes at a time (bb_pipe_bytes.h); bytes stay below 256: new_n <= 255
 #pragma unroll
                     for (int u = 0; u < 8; ++u) w[u] += xs[u];
-                    cw = *(LA uint32_t*)(L + sb + __umul24(jl, FRBS) + lane * 4) | xd;
+                    cw = bbp_centroid_dword8(w, ((uint32_t)new_n + 1u) >> 1);
                 } else {
                     const uint32_t hm1 = (((uint32_t)new_n + 1u) >> 1) - 1u;
 #pragma unroll
@@ -2569,6 +2624,7 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
 #pragma unroll
             for (int i = 0; i < 32; ++i) d += (u64)(v[i] & (0u - xbit(xd, i)));
             const u64 dot = wsum64(d);
+            if constexpr (PROF) lp[3] += 1;
             pph<PROF>(pr, 8);
             s2n = s2T + 2ull * dot + pop;
             accept = decide(dot);
@@ -2700,6 +2756,8 @@ __device__ __forceinline__ void pipe_leaf(LA unsigned char* L, TreeDev* T) {
         pr.ph[15] += st_stale;
         if (lane == 0)
             for (int i = 0; i < 6; ++i) atomicAdd((unsigned long long*)&T->sphase[i], (unsigned long long)det[i]);
+        if (lane == 0)
+            for (int i = 0; i < 5; ++i) atomicAdd((unsigned long long*)&T->lprof[i], (unsigned long long)lp[i]);
     }
     pph_out<PROF>(pr, T, lane);
     (void)helper_lost;
