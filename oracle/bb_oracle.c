@@ -259,6 +259,10 @@ struct Node {
     Node* prev_leaf; /* NULL = the dummy leaf is the predecessor */
     Node* next_leaf;
     int is_leaf;
+    /* the storage model (bbo_tree_storage): observed only, no decision reads them */
+    int st_rec;         /* the length the last compaction (or the image) recorded, -1: none */
+    int st_blocks;      /* 0: full capacity; else the blocks of NG rows a sealed node owns */
+    uint64_t st_thawed; /* serial of the insertion that thawed the node last */
 };
 
 struct bbo_tree {
@@ -289,7 +293,19 @@ struct bbo_tree {
     uint64_t tie_depth[8]; /* edge[3] by the depth of the node searched (root = 1; the last entry takes 8 and deeper) */
     /* bbo_tree_split_counts: observed only, no decision reads them */
     uint64_t split[BBO_SPLIT_COUNTS];
+    /* the storage model (bbo_tree_storage, bbo_tree_thaw_counts): observed only, no decision reads them */
+    uint64_t st_used, st_runs, st_cold, st_full, st_thaws;
+    int st_pools;          /* the engine owns node pools: something was inserted since create or a change of bf */
+    uint64_t st_serial;    /* insertions so far */
+    uint64_t st_sealed_at; /* st_serial at the last compaction or load */
+    int st_above;          /* descent: 0 the node above was not thawed by this insertion, 1 it was, -1 there is none */
+    int st_path_thaws;     /* descent: thaws of this insertion so far */
+    uint64_t thaw[BBO_THAW_COUNTS];
 };
+
+#define BBO_NG 4
+static inline uint64_t st_node_blocks(int rows) { return (uint64_t)((rows + BBO_NG - 1) / BBO_NG); }
+static inline uint64_t st_full_blocks(const bbo_tree* t) { return st_node_blocks(t->bf + 1); }
 
 static Sub* sub_new(const bbo_tree* t) {
     Sub* s = (Sub*)calloc(1, sizeof(Sub));
@@ -349,7 +365,42 @@ static Node* node_new(const bbo_tree* t) {
     nd->subs = (Sub**)calloc((size_t)t->bf + 1, sizeof(Sub*));
     nd->cents = (uint8_t*)malloc((size_t)(t->bf + 1) * (size_t)t->nbytes);
     nd->cards = (uint32_t*)calloc((size_t)t->bf + 1, sizeof(uint32_t));
+    nd->st_rec = -1;
     return nd;
+}
+
+/* thaw_node: a sealed node that an insertion meets on its way down moves to a fresh full-capacity block and loses its
+ * record; the blocks it leaves stay in the used part of the pools until the next compaction.  -> 1 if it was sealed. */
+static int st_visit(bbo_tree* t, Node* nd, int depth) {
+    int above = t->st_above;
+    int th = 0;
+    if (nd->st_blocks != 0) {
+        th = 1;
+        nd->st_blocks = 0;
+        nd->st_rec = -1;
+        nd->st_thawed = t->st_serial;
+        t->st_thaws++;
+        t->st_used += st_full_blocks(t);
+        t->st_path_thaws++;
+        if (nd->is_leaf) {
+            t->thaw[0]++;
+            if (!nd->prev_leaf) t->thaw[2]++;
+            if (!nd->next_leaf) t->thaw[3]++;
+            if (nd->prev_leaf && nd->next_leaf) t->thaw[4]++;
+            if (above == 1) t->thaw[5]++;
+            /* the parent is no root (depth > 2) and was not sealed when this insertion met it: after a sealing of every node
+             * that means an earlier insertion thawed it - the kernels' "sealed leaf under a thawed leaf-parent" */
+            if (above == 0 && depth > 2) t->thaw[17]++;
+        } else {
+            t->thaw[1]++;
+            if (nd->subs[0]->child->is_leaf) t->thaw[15]++;
+            else if (depth == 2) t->thaw[16]++;
+        }
+    } else if (nd->st_rec >= 0 && nd != t->root) {
+        t->thaw[14]++;
+    }
+    t->st_above = th;
+    return th;
 }
 
 static void node_set_row(const bbo_tree* t, Node* nd, int row, Sub* s) {
@@ -623,6 +674,12 @@ static void split_node(bbo_tree* t, Node* node, Sub** outA, Sub** outB, int is_r
     free(old);
     t->stats[4]++;
     t->stats[5]++;
+    /* storage model: node1 is new (full capacity, no record); `node` stays where it is and split_node (bb_tree.hip) rewrites
+     * only its length word, so it keeps its record */
+    t->st_used += st_full_blocks(t);
+    if (node->st_rec >= 0 && node->st_rec == node->len) t->thaw[13]++;
+    if (node->st_thawed == t->st_serial && t->st_serial) t->thaw[node->is_leaf ? 8 : 9]++;
+    if (node->is_leaf && node->st_thawed > t->st_sealed_at) t->thaw[12]++;
     *outA = A;
     *outB = B;
 }
@@ -630,6 +687,8 @@ static void split_node(bbo_tree* t, Node* node, Sub** outA, Sub** outB, int is_r
 /* _BFNode.insert_bf_subcluster, bitbirch.py:305-357 */
 static int node_insert(bbo_tree* t, Node* node, Sub* S, int depth) {
     if ((uint64_t)depth > t->stats[6]) t->stats[6] = (uint64_t)depth;
+    const int st_th = st_visit(t, node, depth);
+    const int st_len = node->len;
     if (node->len == 0) {
         S->id = t->next_id++;
         node_append(t, node, S);
@@ -673,6 +732,7 @@ static int node_insert(bbo_tree* t, Node* node, Sub* S, int depth) {
             t->last_leaf_id = T->id;
             t->last_merged = 1;
             t->stats[2]++;
+            if (st_th) t->thaw[6]++;
             return 0;
         }
         S->id = t->next_id++;
@@ -680,6 +740,10 @@ static int node_insert(bbo_tree* t, Node* node, Sub* S, int depth) {
         t->last_leaf_id = S->id;
         t->last_merged = 0;
         t->stats[3]++;
+        if (st_th) {
+            t->thaw[7]++;
+            t->thaw[18 + st_len % BBO_NG]++;
+        }
         return node->len > t->bf;
     }
     if (node_insert(t, T->child, S, depth + 1)) {
@@ -707,11 +771,20 @@ static void tree_init_root(bbo_tree* t) { /* _initialize_tree, bitbirch.py:880-8
 
 static void tree_insert(bbo_tree* t, Sub* S) {
     if (!t->root) tree_init_root(t);
+    t->st_serial++;
+    t->st_pools = 1;
+    t->st_above = -1;
+    t->st_path_thaws = 0;
     if (node_insert(t, t->root, S, 1)) { /* bitbirch.py:778-782 */
         Sub *A, *B;
         split_node(t, t->root, &A, &B, 1);
         Node* nr = node_new(t);
         t->stats[5]++;
+        t->st_used += st_full_blocks(t);
+        if (t->st_path_thaws) t->thaw[10]++;
+        /* stats[6] is the tree's depth before the new root (all leaves lie on the last level): depth - 1 thaws are every
+         * node of the path below the root, the case "a thaw and a split on every level up to a new root" */
+        if (t->st_path_thaws >= (int)t->stats[6] - 1 && t->st_path_thaws >= 2) t->thaw[11]++;
         node_append(t, nr, A);
         node_append(t, nr, B);
         t->root = nr;
@@ -754,6 +827,7 @@ bbo_tree* bbo_tree_create(int32_t branching_factor, double threshold, int32_t cr
     t->new_ls = (uint32_t*)malloc((size_t)t->F * sizeof(uint32_t));
     t->tmp_cent = (uint8_t*)malloc((size_t)t->nbytes);
     alloc_scratch(t);
+    t->st_used = st_full_blocks(t);
     return t;
 }
 
@@ -767,6 +841,11 @@ void bbo_tree_reset(bbo_tree* t) {
     memset(t->edge, 0, sizeof(t->edge));
     memset(t->tie_depth, 0, sizeof(t->tie_depth));
     memset(t->split, 0, sizeof(t->split));
+    /* bbh_tree_reset (init_empty): one empty root at full capacity, the statistics (the thaw count among them) restart; the
+     * pools and the compaction counters of the handle stay */
+    t->st_used = st_full_blocks(t);
+    t->st_thaws = 0;
+    memset(t->thaw, 0, sizeof(t->thaw));
 }
 
 void bbo_tree_destroy(bbo_tree* t) {
@@ -795,6 +874,8 @@ void bbo_tree_set_merge(bbo_tree* t, int32_t criterion, double tolerance,
         if (t->root == NULL) {
             t->bf = branching_factor;
             alloc_scratch(t);
+            t->st_used = st_full_blocks(t); /* (the engine frees its pools and starts as a fresh handle does) */
+            t->st_pools = 0;
         }
     }
 }
@@ -849,6 +930,75 @@ int bbo_tree_fit_buffers(bbo_tree* t, const void* bufs, int32_t width, int64_t k
     }
     return 0;
 }
+
+/* ---- the storage model: "Node storage" at the top of bb_tree.hip, restated on the oracle's nodes ---------------------- */
+
+typedef struct StWalk {
+    uint64_t used, cold, full, sealed, live;
+} StWalk;
+
+/* k_gc_size and k_gc_move for one node (mode 0 / 1: bbo_tree_compact(seal)), k_img_size and k_img_pack (mode 2), or
+ * counting only (mode 3) */
+static void st_walk(bbo_tree* t, Node* nd, int mode, StWalk* w) {
+    const uint64_t fullb = st_full_blocks(t);
+    if (mode != 3) {
+        int cold;
+        if (mode == 2)
+            cold = nd != t->root;
+        else
+            cold = mode == 1 && nd != t->root && (nd->st_blocks != 0 || nd->st_rec == nd->len);
+        uint64_t blocks = cold ? st_node_blocks(nd->len > 0 ? nd->len : 1) : fullb;
+        nd->st_blocks = blocks == fullb ? 0 : (int)blocks;
+        nd->st_rec = nd->len;
+        w->used += blocks;
+        if (cold) w->cold++; else w->full++;
+    }
+    w->live++;
+    if (nd->st_blocks != 0) w->sealed++;
+    if (!nd->is_leaf)
+        for (int i = 0; i < nd->len; ++i) st_walk(t, nd->subs[i]->child, mode, w);
+}
+
+void bbo_tree_compact(bbo_tree* t, int32_t seal) {
+    if (!t->st_pools) return; /* bbh_tree_compact: nothing was ever inserted, no pools */
+    StWalk w = {0, 0, 0, 0, 0};
+    if (t->root) {
+        st_walk(t, t->root, seal != 0, &w);
+    } else { /* a reset tree: the empty root */
+        w.used = st_full_blocks(t);
+        w.full = 1;
+    }
+    t->st_used = w.used;
+    t->st_cold = w.cold;
+    t->st_full = w.full;
+    t->st_runs++;
+    t->st_sealed_at = t->st_serial;
+}
+
+void bbo_tree_mark_loaded(bbo_tree* t) {
+    t->st_runs = t->st_cold = t->st_full = 0;
+    if (!t->st_pools || !t->root) return; /* (an image without nodes loads into a fresh handle) */
+    StWalk w = {0, 0, 0, 0, 0};
+    st_walk(t, t->root, 2, &w);
+    t->st_used = w.used;
+    t->st_sealed_at = t->st_serial;
+}
+
+void bbo_tree_storage(const bbo_tree* t, uint64_t* out8) {
+    StWalk w = {0, 0, 0, 0, 0};
+    if (t->root) st_walk((bbo_tree*)t, t->root, 3, &w);
+    else w.live = 1;
+    out8[0] = t->st_pools ? t->st_used : 0;
+    out8[1] = t->st_runs;
+    out8[2] = t->st_cold;
+    out8[3] = t->st_full;
+    out8[4] = t->st_thaws;
+    out8[5] = w.sealed;
+    out8[6] = w.live;
+    out8[7] = (uint64_t)t->st_pools;
+}
+
+void bbo_tree_thaw_counts(const bbo_tree* t, uint64_t* out) { memcpy(out, t->thaw, sizeof(t->thaw)); }
 
 int64_t bbo_tree_leaf_count(const bbo_tree* t) {
     int64_t c = 0;

@@ -134,6 +134,37 @@ void bbo_tree_split_counts(const bbo_tree* t, uint64_t* out24);
 void bbo_tree_walk(const bbo_tree* t, int64_t* n_nodes, int64_t* n_rows, int32_t* nodes, uint64_t* row_n, uint32_t* row_id,
                    uint32_t* row_popcount, uint8_t* row_centroids, uint64_t* row_linear_sums);
 
+
+/* ---- the storage model: how the engine keeps its nodes ("Node storage", bblean_amd/csrc/bb_tree.hip) --------------------
+ * The reference's node is a Python list; the engine packs nodes in blocks of 4 rows, seals nodes in a compaction and thaws
+ * them when an insertion reaches them.  The oracle follows that on its own nodes: per node a recorded length (none, or a
+ * value) and a capacity (full, or sealed at ceil(max(len, 1) / 4) blocks).  It only observes: no result of any other call
+ * depends on it.  Every sealed node an insertion meets on its way down is thawed, the root first. */
+/* gc_nodes (k_gc_size, k_gc_move): a node is cold when `seal` is set, it is not the root, and it is sealed already or its
+ * recorded length equals its length; a cold node gets its length rounded up to blocks (full capacity when that is as many
+ * blocks), every other node full capacity; every node records its length.  Nothing happens on a tree that never received
+ * anything (bbh_tree_compact). */
+void bbo_tree_compact(bbo_tree* t, int32_t seal);
+/* what bbh_tree_load_fd leaves (k_img_size, k_img_pack): the root full, every other node at its rounded length, every length
+ * recorded, the compaction counters those of a fresh handle, the thaw count that of the saved tree. */
+void bbo_tree_mark_loaded(bbo_tree* t);
+/* [0]=blocks in the used part of the node pools (0: no pools yet), [1]=compactions, [2]=cold nodes and [3]=full nodes of the
+ * last one, [4]=thaws since create or reset, [5]=nodes sealed now, [6]=live nodes, [7]=1 once the tree owns pools */
+void bbo_tree_storage(const bbo_tree* t, uint64_t* out8);
+/* what the thaws met, since create or reset; no decision reads them.  Thaws ...
+ * [0] of leaves, [1] of internal nodes, of a leaf that was [2] the first of the chain, [3] the last, [4] neither,
+ * [5] of a leaf whose parent the same insertion thawed, [6] of a leaf that then took a merge (no length changes),
+ * [7] of a leaf that then took an append, [8] of a leaf / [9] of an internal node that the same insertion then split,
+ * [10] insertions that thawed a node and made a new root, [11] those that thawed every node below the root,
+ * [12] splits of a leaf that was thawed since the last compaction or load,
+ * [13] splits after which the half that stayed in place has exactly its recorded length (it keeps the record),
+ * [14] visits of a node other than the root that has a record and full capacity (cold but not sealed: no thaw),
+ * [15] of an internal node whose children are leaves, [16] of another internal node directly under the root,
+ * [17] of a leaf on level 3 or deeper whose parent was at full capacity already (thawed since the sealing),
+ * [18..21] of a leaf of length = 0, 1, 2, 3 (mod 4) that then took an append.  [22], [23] are zero. */
+#define BBO_THAW_COUNTS 24
+void bbo_tree_thaw_counts(const bbo_tree* t, uint64_t* out24);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,11 @@ _W = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
 SPLIT_COUNTS = ("splits", "internal", "root", "majority_tie", "argmin1_tie", "argmin2_tie", "equal_sims", "equal_sims_pairs_differ",
                 "fp1_is_fp2", "n1_eq_n2", "n1_gt_n2", "small_over_255", "small_over_65535", "small_mod16_0", "small_mod16_1", "zero_row",
                 "small_all_single", "small_u8_with_single", "small_over_16", "m_over_124", "fp1_row0", "fp1_last_row", "_22", "_23")
+# bbo_tree_storage and bbo_tree_thaw_counts, in their order (bb_oracle.h)
+STORAGE = ("used_blocks", "runs", "cold", "full", "thaws", "sealed_now", "live", "pools")
+THAW_COUNTS = ("leaf", "internal", "first_leaf", "last_leaf", "middle_leaf", "parent_thawed_too", "then_merge", "then_append", "leaf_then_split",
+               "internal_then_split", "then_new_root", "whole_path_new_root", "thawed_leaf_splits", "in_place_half_keeps_record", "cold_but_full", "leaf_parent",
+               "top_level", "leaf_under_thawed_parent", "append_len0", "append_len1", "append_len2", "append_len3", "_22", "_23")
 
 
 def oracle_lib() -> C.CDLL:
@@ -52,6 +57,10 @@ def oracle_lib() -> C.CDLL:
         "bbo_tree_edge_counts": (None, [vp, vp]),
         "bbo_tree_tie_depths": (None, [vp, vp]),
         "bbo_tree_split_counts": (None, [vp, vp]),
+        "bbo_tree_compact": (None, [vp, i32]),
+        "bbo_tree_mark_loaded": (None, [vp]),
+        "bbo_tree_storage": (None, [vp, vp]),
+        "bbo_tree_thaw_counts": (None, [vp, vp]),
         "bbo_tree_walk": (None, [vp, C.POINTER(i64), C.POINTER(i64), vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
@@ -145,6 +154,26 @@ class OracleEngine:
         out = np.zeros(24, dtype=np.uint64)
         self.lib.bbo_tree_split_counts(self._h, out.ctypes.data)
         return {name: int(v) for name, v in zip(SPLIT_COUNTS, out)}
+
+    def compact(self, seal):
+        r"""The storage model's compaction (bbo_tree_compact): the tree itself does not change."""
+        self.lib.bbo_tree_compact(self._h, int(seal))
+
+    def reload(self):
+        r"""The storage model's state after a save and bbh_tree_load_fd (bbo_tree_mark_loaded)."""
+        self.lib.bbo_tree_mark_loaded(self._h)
+
+    def storage(self):
+        r"""name -> value of the storage model (STORAGE, bb_oracle.h)."""
+        out = np.zeros(8, dtype=np.uint64)
+        self.lib.bbo_tree_storage(self._h, out.ctypes.data)
+        return {name: int(v) for name, v in zip(STORAGE, out)}
+
+    def thaw_counts(self):
+        r"""name -> how many thaws met that condition since create or reset (THAW_COUNTS, bb_oracle.h)."""
+        out = np.zeros(24, dtype=np.uint64)
+        self.lib.bbo_tree_thaw_counts(self._h, out.ctypes.data)
+        return {name: int(v) for name, v in zip(THAW_COUNTS, out)}
 
     def walk(self):
         r"""The whole tree in pre-order (the root first, then the subtrees of its rows in row order), as

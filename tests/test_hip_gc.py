@@ -3,7 +3,11 @@ node pools seals nodes that stopped changing (their length rounded up to a block
 is a Python list that grows, bitbirch.py:264-287) and renumbers every node; an insertion that reaches a sealed node moves it
 back to full capacity first (the complete engine; the steady-state and the pipelined kernel hand such elements over).  None of
 this may change a result: every test here forces compactions at the worst moments - at every pool exhaustion, with pools that
-run out every few elements, between `fit` calls - and compares per element with the CPU oracle."""
+run out every few elements, between `fit` calls - and compares per element with the CPU oracle.
+
+Random rows, leaves and counters only.  What a compaction or a thaw leaves in the tracking rows, child links and the leaf chain,
+which nodes a compaction seals and how many thaws a fit costs is held, case by crafted case, by test_hip_tree_storage.py
+(the tree image's walk and bbh_tree_memory against the oracle's storage model)."""
 import os
 
 import numpy as np

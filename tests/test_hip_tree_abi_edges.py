@@ -173,6 +173,28 @@ class Raw:
         ok(self.lib, self.lib.bbh_tree_kernel_counts(self.h, at(out)))
         return [int(v) for v in out]
 
+    def compact(self, seal):
+        ok(self.lib, self.lib.bbh_tree_compact(self.h, int(seal)))
+
+    def memory(self):
+        r"""bbh_tree_memory: [pool bytes, used bytes, cluster-feature bytes, peak, compactions, sealed and full nodes of the last
+        one, thaws]."""
+        out = np.zeros(8, np.uint64)
+        ok(self.lib, self.lib.bbh_tree_memory(self.h, at(out)))
+        return [int(v) for v in out]
+
+    def reload(self):
+        r"""Save the image, load it into a new handle (bbh_tree_load_fd), destroy the old handle and go on with the new one."""
+        with tempfile.TemporaryFile() as f:
+            written = C.c_uint64(0)
+            ok(self.lib, self.lib.bbh_tree_save_fd(self.h, f.fileno(), 0, C.byref(written)))
+            f.seek(0)
+            new = C.c_void_p()
+            ok(self.lib, self.lib.bbh_tree_load_fd(C.byref(new), f.fileno(), 0, 0))
+            assert new.value and os.lseek(f.fileno(), 0, os.SEEK_CUR) == written.value, written.value
+        ok(self.lib, self.lib.bbh_tree_destroy(self.h))
+        self.h = new
+
     def save_image(self) -> bytes:
         r"""The tree's image (bbh_tree_save_fd into a temporary file); the tree stays as it was."""
         with tempfile.TemporaryFile() as f:

@@ -7,6 +7,8 @@ A case is a tree configuration (`cfg`) and a list of operations:
     ("buffers", table)                             table: (k, F + 1) unsigned, [linear_sum | n_samples]
     ("set_merge", crit, tolerance, tol_table, threshold, bf)
     ("reset",)
+    ("compact", seal)                              bbh_tree_compact; on the oracle the storage model's compaction
+    ("reload",)                                    save, bbh_tree_load_fd into a new handle, go on with that one
 `replay` runs them on tests/oracle_engine.OracleEngine and returns everything observable."""
 from __future__ import annotations
 
@@ -349,6 +351,10 @@ def apply_op(eng, op):
         return eng.set_merge(op[1], op[2], np.asarray(op[3], dtype=np.float64), op[4], op[5])
     if op[0] == "reset":
         return eng.reset()
+    if op[0] == "compact":
+        return eng.compact(op[1])
+    if op[0] == "reload":
+        return eng.reload()
     raise ValueError(op[0])
 
 
