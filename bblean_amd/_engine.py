@@ -202,6 +202,39 @@ class HipEngine:
         )
         return out
 
+    def route_packed(
+        self, rows: object, stream: int | None = None
+    ) -> tuple[NDArray[np.uint32], NDArray[np.uint8], NDArray[np.uint32], NDArray[np.uint32]]:
+        r"""Route packed fingerprints (as for `fit_packed`) through the tree without inserting them:
+        ``(leaf_ids, accept, inter, union)`` per row - the leaf BitFeature an insertion would choose, whether the merge
+        criterion would accept the row there, and the exact counts against that BitFeature's centroid.  The tree is
+        only read (`bbh_tree_route_packed`)."""
+        if _is_device_tensor(rows):
+            if rows.stride(1) != 1:  # type: ignore[attr-defined]
+                rows = rows.contiguous()  # type: ignore[attr-defined]
+            n, nb = int(rows.shape[0]), int(rows.shape[1])  # type: ignore[attr-defined]
+            stride = int(rows.stride(0))  # type: ignore[attr-defined]
+            keep = rows
+            if stream is None:
+                stream = _launch_stream(rows)
+        else:
+            keep = np.ascontiguousarray(rows, dtype=np.uint8)
+            n, nb = keep.shape
+            stride = nb
+        if nb != self.nbytes:
+            raise RuntimeError(f"rows have {nb} bytes, tree expects {self.nbytes}")
+        leaf = np.empty(n, dtype=np.uint32)
+        accept = np.empty(n, dtype=np.uint8)
+        inter = np.empty(n, dtype=np.uint32)
+        union = np.empty(n, dtype=np.uint32)
+        _lib.check(
+            self._lib.bbh_tree_route_packed(
+                self._h, _lib.ptr(keep), n, stride, leaf.ctypes.data, accept.ctypes.data, inter.ctypes.data,
+                union.ctypes.data, stream
+            )
+        )
+        return leaf, accept, inter, union
+
     @staticmethod
     def fit_packed_many(engines: "list[HipEngine]", rows_list: list) -> list[NDArray[np.uint32]]:
         r"""Insert into several trees with ONE kernel launch (one workgroup per tree)."""

@@ -621,6 +621,57 @@ class BitBirch:
             off, ind, dist = off.cpu().numpy(), ind.cpu().numpy(), dist.cpu().numpy()
         return off, ind.astype(np.int64), dist
 
+    def route(self, X, input_is_packed: bool = True, n_features: int | None = None, sort: bool = True):  # type: ignore[no-untyped-def]
+        r"""Route fingerprints through the fitted tree WITHOUT inserting them: ``(cluster, accept, sim)``, one entry per row.
+
+        ``cluster`` (int64) is the position, in `get_centroids(sort=sort)` / `get_cluster_mol_ids(sort=sort)`, of the cluster
+        the greedy descent of `fit` reaches for that row; ``accept`` (bool) whether the current merge criterion would let the
+        row join it (False: a `fit` would start a new cluster there); ``sim`` (float64) the Tanimoto similarity of the row to
+        that cluster's centroid.  This is the tree's own answer in about depth x branching_factor compares per row - not the
+        globally nearest centroid, which `sklearn.BitBirch.predict` searches the whole table for.  The model is not changed.
+        Input as for `fit` (packed or unpacked rows, a list of rows, a device-resident ``torch.uint8`` tensor of packed
+        rows)."""
+        self._require_init()
+        if self._only_has_leaves:
+            raise ValueError("Internal nodes were released: there is no tree to route through")
+        route_packed = getattr(self._engine, "route_packed", None)
+        if route_packed is None:
+            raise NotImplementedError(f"{type(self._engine).__name__} has no route_packed: routing needs an engine that can walk its tree")
+        is_dev = hasattr(X, "data_ptr") and getattr(X, "is_cuda", False)
+        if is_dev:
+            if not input_is_packed:
+                raise ValueError("device-resident input must be packed uint8")
+            if X.shape[0] == 0:
+                raise ValueError("Input must have at least 1 fingerprint")
+            nf = X.shape[1] * 8 if n_features is None else n_features
+            if X.shape[1] * 8 < nf:
+                raise ValueError("n_features is larger than the padded length, which is inconsistent")
+            rows: tp.Any = X
+        else:
+            nf = _validate_n_features(X, input_is_packed, n_features)
+            arr = np.stack(X) if isinstance(X, list) else np.asarray(X)
+            if input_is_packed:
+                rows = np.ascontiguousarray(arr, dtype=np.uint8)
+                if rows.shape[1] * 8 != nf:
+                    rows = pack_fingerprints(unpack_fingerprints(rows, nf))
+            else:
+                rows = pack_fingerprints(arr.astype(np.uint8, copy=False))
+        if nf != self._n_features:
+            raise ValueError(f"tree was built with n_features={self._n_features}, got {nf}")
+        self._push_merge_to_engine()  # (the criterion a `fit` would act on now)
+        leaf, accept, inter, union = route_packed(rows)
+        lv = self._leaves()
+        pos_of_id = np.full(int(lv["ids"].max(initial=0)) + 1, -1, dtype=np.int64)
+        pos_of_id[lv["ids"]] = np.arange(lv["ids"].size, dtype=np.int64)
+        order = self._leaf_order(sort)
+        rank = np.empty(order.size, dtype=np.int64)
+        rank[order] = np.arange(order.size, dtype=np.int64)  # chain position -> position in get_centroids(sort=sort)
+        chain = pos_of_id[np.asarray(leaf, dtype=np.int64)]
+        if (chain < 0).any():
+            raise RuntimeError("the engine routed a row to a BitFeature id that is not a leaf of the tree")
+        sim = np.asarray(inter, dtype=np.float64) / np.maximum(np.asarray(union, dtype=np.float64), 1.0)
+        return rank[chain], np.asarray(accept).astype(bool), sim
+
     def get_centroids_mol_ids(self, sort: bool = True, packed: bool = True) -> dict[str, list]:
         r"""(reference bitbirch.py:895-907)"""
         return {

@@ -2213,6 +2213,7 @@ __global__ __launch_bounds__(TB, 2) void k_tree_insert_dense(TreeDev* trees) {
 #include "bb_tree_fast.inc"
 #include "bb_tree_pipe.inc"
 #include "bb_tree_sys.inc"
+#include "bb_tree_route.inc"
 #if defined(__HIPCC__)
 
 // the complete engine compiled for the benchmark shape with phase timers (tools/phases.py with BBHIP_NO_FAST=1)
@@ -3602,6 +3603,70 @@ extern "C" int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, 
         }
     }
     BB_TRY(o.finish(s));
+    BB_HIP(hipStreamSynchronize(s));
+    return BBH_OK;
+}
+
+// Route packed fingerprints through the tree as it stands, read-only (bb_tree_route.inc): the leaf row an insertion would
+// choose, whether it would merge, and the exact counts against that row's centroid.
+static int route_launch(bbh_tree* t, const uint8_t* rows_dev, int64_t row_stride, int64_t n, uint32_t* out_leaf, uint8_t* out_accept,
+                        uint32_t* out_inter, uint32_t* out_union, uint32_t* err, hipStream_t s) {
+    const TreeDev& h = t->h;
+    const size_t lds = route_layout(h.bf, h.RB).total;
+    bb::ProfScope ps("tree_route", s);
+    ps.units((long long)n);
+    const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)ROUTE_GRID_MAX);
+    hipLaunchKernelGGL(k_tree_route, dim3(grid), dim3(TB), lds, s, h, rows_dev, (long long)row_stride, (long long)n, out_leaf, out_accept,
+                       out_inter, out_union, err);
+    BB_HIP(hipGetLastError());
+    return BBH_OK;
+}
+
+extern "C" int bbh_tree_route_packed(bbh_tree* t, const uint8_t* rows, int64_t n, int64_t row_stride, uint32_t* out_leaf,
+                                     uint8_t* out_accept, uint32_t* out_inter, uint32_t* out_union, void* stream) {
+    if (!t) return bb::fail(BBH_ERR_INVALID, "null tree");
+    if (n < 0 || row_stride < t->h.nbytes) return bb::fail(BBH_ERR_INVALID, "rows must be (n, n_features/8) uint8");
+    if (n == 0) return BBH_OK;
+    if (!rows) return bb::fail(BBH_ERR_INVALID, "null rows with n > 0");
+    if (t->lazy_pools || t->h.node_hdr == nullptr || t->h.ctr[C_IDS] == 0)
+        return bb::fail(BBH_ERR_STATE, "the tree holds nothing to route to: fit it first");
+    BB_HIP(hipSetDevice(t->device));
+    hipStream_t s = (hipStream_t)stream;
+    bb::DevOut ol, oa, oi, ou;
+    BB_TRY(ol.init(out_leaf, (size_t)n * 4));
+    BB_TRY(oa.init(out_accept, (size_t)n));
+    BB_TRY(oi.init(out_inter, (size_t)n * 4));
+    BB_TRY(ou.init(out_union, (size_t)n * 4));
+    bb::DevScope tmp(s);
+    uint32_t* err = nullptr;
+    BB_HIP(tmp.get(&err, 4));
+    BB_HIP(hipMemsetAsync(err, 0, 4, s));
+    auto at = [](bb::DevOut& o, int64_t off, size_t elem) { return o.dev ? (uint8_t*)o.dev + (size_t)off * elem : nullptr; };
+    if (bb::is_device_ptr(rows)) {
+        BB_TRY(route_launch(t, rows, row_stride, n, (uint32_t*)ol.dev, (uint8_t*)oa.dev, (uint32_t*)oi.dev, (uint32_t*)ou.dev, err, s));
+    } else {
+        HostSlabs slabs;
+        BB_TRY(slabs.init(t->device, rows, (size_t)row_stride, (size_t)t->h.nbytes, n));
+        for (int64_t off = 0; off < n;) {
+            const uint8_t* d = nullptr;
+            int64_t m = 0;
+            BB_TRY(slabs.acquire(off, &d, &m));
+            BB_TRY(route_launch(t, d, row_stride, m, (uint32_t*)at(ol, off, 4), at(oa, off, 1), (uint32_t*)at(oi, off, 4),
+                                (uint32_t*)at(ou, off, 4), err, s));
+            BB_TRY(tmp.sync("tree_route"));  // (the slab after the next one lands in this slab's buffer)
+            off += m;
+        }
+    }
+    uint32_t herr = 0;
+    BB_HIP(hipMemcpyAsync(&herr, err, 4, hipMemcpyDeviceToHost, s));
+    BB_TRY(tmp.sync("tree_route"));
+    if (herr != 0)
+        return bb::fail(BBH_ERR_CAPACITY, "tree_route: a walk left the tree (deeper than its %u recorded levels, or a corrupt link)",
+                        (unsigned)t->h.ctr[C_DEPTH]);
+    BB_TRY(ol.finish(s));
+    BB_TRY(oa.finish(s));
+    BB_TRY(oi.finish(s));
+    BB_TRY(ou.finish(s));
     BB_HIP(hipStreamSynchronize(s));
     return BBH_OK;
 }

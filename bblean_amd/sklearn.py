@@ -23,6 +23,7 @@ from sklearn.base import (
     TransformerMixin,
     _fit_context,
 )
+from sklearn.exceptions import NotFittedError
 from sklearn.utils.validation import check_is_fitted, validate_data
 
 from bblean_amd._merges import MergeCriterion
@@ -159,6 +160,34 @@ class BitBirch(
             idx = idx.cpu().numpy()
         return self.subcluster_labels_[idx]
 
+    def predict_tree(  # type: ignore[no-untyped-def]
+        self, X, input_is_packed: bool = True, n_features: int | None = None, novel=None, return_accept: bool = False
+    ):
+        """Label (1..K, `predict`'s numbering) of the subcluster the TREE routes every row to: the one a further `fit` would
+        try to merge the row into (`bblean_amd.bitbirch.BitBirch.route`), found in about depth x branching_factor compares
+        per row instead of `predict`'s K.  It need not be the closest centroid.  Rows the merge criterion would not accept
+        there - a `fit` would open a new subcluster for them - get the label `novel` where it is not None;
+        ``return_accept=True`` returns ``(labels, accept)``.  The model is not changed.  A device tensor gives device
+        tensors.  It needs the tree only, so it also works on what `load` returns."""
+        if not getattr(self, "_is_init", False):
+            raise NotFittedError(f"This {type(self).__name__} instance is not fitted yet. Call 'fit' before using this estimator.")
+        dev = _is_dev(X)
+        if dev:
+            if X.dim() != 2 or str(X.dtype) != "torch.uint8":
+                raise ValueError("device-resident input must be a 2-dimensional torch.uint8 tensor of packed rows")
+        elif hasattr(X, "toarray"):
+            X = X.toarray()
+        # (the tree is all it needs: a model that `load` returned has no fitted sklearn attributes, and routes all the same)
+        cluster, accept, _ = self.route(X, input_is_packed=input_is_packed, n_features=n_features, sort=True)
+        labels = cluster + 1  # subcluster_labels_: 1..K in the order of get_centroids(sort=True)
+        if novel is not None:
+            labels = np.where(accept, labels, novel)
+        if dev:
+            import torch
+
+            labels, accept = torch.from_numpy(np.ascontiguousarray(labels)).to(X.device), torch.from_numpy(accept).to(X.device)
+        return (labels, accept) if return_accept else labels
+
     def transform(  # type: ignore[no-untyped-def]
         self, X, input_is_packed: bool = True, n_features: int | None = None
     ):
@@ -269,6 +298,12 @@ class UnpackedBitBirch(BitBirch):
         self, X, input_is_packed: bool = False, n_features: int | None = None
     ):
         return super().predict(X, input_is_packed=input_is_packed, n_features=n_features)
+
+    def predict_tree(  # type: ignore[no-untyped-def]
+        self, X, input_is_packed: bool = False, n_features: int | None = None, novel=None, return_accept: bool = False
+    ):
+        return super().predict_tree(X, input_is_packed=input_is_packed, n_features=n_features, novel=novel,
+                                    return_accept=return_accept)
 
     def transform(  # type: ignore[no-untyped-def]
         self, X, input_is_packed: bool = False, n_features: int | None = None

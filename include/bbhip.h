@@ -280,6 +280,31 @@ int bbh_tree_fit_packed(bbh_tree* t, const uint8_t* rows, int64_t n, int64_t row
 int bbh_trees_fit_packed(bbh_tree** trees, int32_t n_trees, const uint8_t* const* rows,
                          const int64_t* n, const int64_t* row_stride, uint32_t* const* out_leaf,
                          void* stream);
+
+/* Route n packed fingerprints through the tree as it stands WITHOUT inserting them: for each
+ * row, independently, what _BFNode.insert_bf_subcluster (bitbirch.py:305-357) does up to its
+ * first write.  From the root, the first argmax of i / max(u, 1) over the node's rows
+ * (i = popcount(row & q), u = |row| + |q| - i; exact fractions, ties to the lower row) is
+ * followed down to a leaf row.  rows, row_stride, the last-row rule, n == 0 and NULL rows as
+ * for bbh_tree_fit_packed.  Every output is optional (NULL) and may be host or device memory:
+ *   out_leaf[e]    id of the chosen leaf BitFeature (the ids bbh_tree_fit_packed writes and
+ *                  bbh_tree_export_leaves lists);
+ *   out_accept[e]  1 if the tree's current merge criterion (threshold, tolerance, table) would
+ *                  accept the row as a one-fingerprint nominee of that BitFeature, else 0
+ *                  (BBH_CRIT_NEVER: 0; n_samples + 1 beyond 32 bits: 0);
+ *   out_inter[e], out_union[e]  exact counts of the row against that BitFeature's centroid
+ *                  (the true union: 0 when both are empty).
+ * So inserting row e alone into a copy of the tree merges iff out_accept[e] == 1, and then
+ * into out_leaf[e].  The tree is only read: no node is thawed, no pool grows, the counters of
+ * bbh_tree_stats / _kernel_counts / _memory and the bytes of bbh_tree_save_fd stay as they were.
+ * A tree that holds nothing (never fitted, or reset) is BBH_ERR_STATE (after the n == 0 and
+ * NULL checks); a refused call writes nothing.  A walk that would leave the tree (deeper than
+ * its recorded depth, a link beyond the pools) ends the call with BBH_ERR_CAPACITY.
+ * Synchronous.  Profiled as "tree_route", units = rows. */
+int bbh_tree_route_packed(bbh_tree* t, const uint8_t* rows, int64_t n, int64_t row_stride,
+                          uint32_t* out_leaf, uint8_t* out_accept, uint32_t* out_inter,
+                          uint32_t* out_union, void* stream);
+
 /* _fit_buffers for several independent trees in one launch (the trees of a merge round,
  * multiround.py:240-264): tree i inserts k[i] buffers of element width width[i] from bufs[i].
  * NULL bufs[i] with k[i] > 0 are BBH_ERR_INVALID; checked before the first tree is touched. */
