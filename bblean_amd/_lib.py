@@ -43,6 +43,7 @@ _PROTOTYPES = {
     "bbh_jt_dist_matrix": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
     "bbh_jt_topk": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "bbh_jt_radius": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _f64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbh_jt_components": (_int, [_vp, _i64, _i64, _f64, _vp, _vp, _vp, _vp]),
     "bbh_mfma_i8_probe": (_int, [_vp, _vp, _vp, _vp]),
     "bbh_unpack": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "bbh_pack": (_int, [_vp, _i64, _i64, _vp, _vp]),

@@ -621,6 +621,33 @@ class BitBirch:
             off, ind, dist = off.cpu().numpy(), ind.cpu().numpy(), dist.cpu().numpy()
         return off, ind.astype(np.int64), dist
 
+    def centroid_components(self, radius: float | None = None, sort: bool = True) -> tuple[NDArray[np.int64], int]:
+        r"""The connected components of the centroids at Jaccard distance `radius` (default ``1 - threshold``):
+        ``(labels int64 (K,), n_components)`` over the positions of `get_centroids(sort=sort)`.  Two centroids are linked
+        iff `centroid_radius_neighbors(radius)` lists one for the other; components are the transitive closure, labelled by
+        their first member in ascending position, as ``scipy.sparse.csgraph.connected_components`` of that graph - computed
+        on the device without the graph (`similarity.jt_components_packed`).  The model is left as it is."""
+        from bblean_amd import similarity
+
+        radius = similarity._radius_check(1.0 - self.threshold if radius is None else radius)
+        order = self._leaf_order(sort)
+        gather = getattr(self._engine, "gather_centroids", None)
+        cents = gather(order, device_out=True) if gather is not None else np.ascontiguousarray(self._leaves()["cents"][order])
+        labels, count = similarity.jt_components_packed(cents, radius)
+        if hasattr(labels, "cpu"):
+            labels = labels.cpu().numpy()
+        return np.asarray(labels, dtype=np.int64), int(count)
+
+    def link_clusters(self, radius: float | None = None) -> "BitBirch":
+        r"""Merge the clusters whose centroids hang together at Jaccard distance `radius` (default ``1 - threshold``):
+        single-linkage clustering of the centroids cut at `radius`, which is `centroid_components`.  Stores the labels
+        where `global_clustering` stores its own (1-based, in ``sort=True`` order), so every ``global_clusters=True`` getter
+        and `save` / `load` see the merged clusters."""
+        labels, count = self.centroid_components(radius, sort=True)
+        self._global_clustering_centroid_labels = labels + 1
+        self._n_global_clusters = count
+        return self
+
     def route(self, X, input_is_packed: bool = True, n_features: int | None = None, sort: bool = True):  # type: ignore[no-untyped-def]
         r"""Route fingerprints through the fitted tree WITHOUT inserting them: ``(cluster, accept, sim)``, one entry per row.
 

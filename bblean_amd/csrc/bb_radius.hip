@@ -17,30 +17,11 @@
 // knows where its hits start, walks its range again and writes them in ascending row index.  The output therefore does
 // not depend on the order in which workgroups run, nor (ranges ascend too) on how the table was split.
 #include "bb_common.h"
+#include "bb_radius_common.h"  // jaccard_dist, k_radius_table, radius_ranges
 
 using namespace bbd;
 
 namespace {
-
-__device__ __forceinline__ double jaccard_dist(uint32_t inter, uint32_t un) {
-    return un == 0u ? 0.0 : (double)(un - inter) / (double)un;
-}
-
-// imin[u] for u = 0 .. nbits: bisection on the monotone predicate jaccard_dist(i, u) <= radius
-__global__ __launch_bounds__(256) void k_radius_table(double radius, int nbits, uint16_t* __restrict__ tab) {
-    const int u = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (u > nbits) return;
-    int lo = 0, hi = u + 1;  // the answer lies in [lo, hi]; hi = u + 1 is "none"
-    if (jaccard_dist((uint32_t)u, (uint32_t)u) <= radius) {
-        hi = u;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (jaccard_dist((uint32_t)mid, (uint32_t)u) <= radius) hi = mid;
-            else lo = mid + 1;
-        }
-    }
-    tab[u] = (uint16_t)hi;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // AND + popcount.  Every lane owns one query row in registers; table rows are wave-uniform (scalar loads).  Grid:
@@ -221,17 +202,6 @@ __global__ __launch_bounds__(1024) void k_radius_scan(int64_t nq, int64_t* __res
     }
 }
 
-int cu_count() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
-    return n;
-}
-
 }  // namespace
 
 extern "C" int bbh_jt_radius(const uint8_t* queries, int64_t nq, int64_t q_stride, const uint8_t* rows, int64_t nc,
@@ -268,8 +238,7 @@ extern "C" int bbh_jt_radius(const uint8_t* queries, int64_t nq, int64_t q_strid
     int64_t* offd = (int64_t*)oo.dev;
 
     const bool al4 = (uintptr_t)qd % 4 == 0 && (uintptr_t)cd % 4 == 0 && q_stride % 4 == 0;
-    const bool fast = al4 && (nbytes == 8 || nbytes == 16 || nbytes == 32 || nbytes == 64 || nbytes == 128 ||
-                              nbytes == 256);
+    const bool fast = al4 && radius_fast_width(nbytes);
 
     uint32_t* ccard = nullptr;
     BB_HIP(tmp.get(&ccard, (size_t)nc * 4));
@@ -278,14 +247,9 @@ extern "C" int bbh_jt_radius(const uint8_t* queries, int64_t nq, int64_t q_strid
     {
         bb::ProfScope ps("jt_radius", s);
         ps.units(nq);
-        // the ranges of bbh_jt_assign: fill the device four times over, with at least 64 rows per range
-        const int64_t qblocks = fast ? (nq + 255) / 256 : (nq + 3) / 4;
-        int64_t want = (4 * (int64_t)cu_count() + qblocks - 1) / qblocks;
-        const int64_t most = (nc + 63) / 64;
-        if (want > most) want = most;
-        if (want > 65535) want = 65535;
-        const int per = (int)((nc + want - 1) / want);
-        const int nsplit = (int)((nc + per - 1) / per);
+        int64_t qblocks = 0;
+        int per = 0, nsplit = 0;
+        radius_ranges(nq, nc, fast, 4, &qblocks, &per, &nsplit);
         int* part = nullptr;
         uint16_t* tab = nullptr;
         BB_HIP(tmp.get(&part, (size_t)nsplit * nq * 4));

@@ -45,6 +45,7 @@ __all__ = [
     "jt_dist_matrix_packed",
     "jt_topk_packed",
     "jt_radius_packed",
+    "jt_components_packed",
     "jt_compl_isim_segments",
     "jt_cluster_stats_segments",
 ]
@@ -456,6 +457,50 @@ def jt_radius_packed(queries: object, rows: object, radius: float, exclude: obje
         order = np.lexsort((dist, np.repeat(np.arange(nq), np.diff(offsets))))  # stable: equal distances keep the index order
         idx, dist, inter, union = idx[order], dist[order], inter[order], union[order]
     return (offsets, idx, dist, inter, union) if return_counts else (offsets, idx, dist)
+
+
+def jt_components_packed(rows: object, radius: float, return_roots: bool = False):  # type: ignore[no-untyped-def]
+    r"""The connected components of a packed table at Jaccard distance ``radius``: ``(labels, n_components)``.  Rows ``a``
+    and ``b`` are linked iff ``jt_radius_packed(rows, rows, radius)`` reports the pair (``(u - i) / u <= radius`` as one
+    float64 division, 0.0 where ``u == 0``; a pair at ``radius`` bit for bit is linked); components are the transitive
+    closure, i.e. single-linkage clustering cut at ``radius``.  ``labels[v]`` is the rank of the component's first row
+    among the first rows of all components, which is the labelling of
+    ``scipy.sparse.csgraph.connected_components(d <= radius, directed=False)`` - without the graph: no edge is stored.
+    With ``return_roots`` the first row of every row's component follows.  ``radius = 0`` groups duplicates, ``radius < 0``
+    leaves every row alone, ``radius >= 1`` gives one component.
+
+    NumPy rows -> int64 NumPy labels (and roots); a device tensor -> device tensors, int32 as `jt_topk_packed`'s indices,
+    on the current stream (the call synchronises it)."""
+    radius = _radius_check(radius)
+    if not _is_dev(rows):
+        arr = np.asarray(rows)
+        if arr.ndim == 2 and arr.dtype != np.uint8:
+            raise TypeError(f"rows must be packed uint8, got {arr.dtype}")
+    elif str(rows.dtype) != "torch.uint8":  # type: ignore[attr-defined]
+        raise TypeError(f"rows must be packed uint8, got {rows.dtype}")  # type: ignore[attr-defined]
+    c, n, nb, stride = _u8_2d(rows, "rows")
+    if nb < 1:
+        raise RuntimeError("rows must have at least one byte per row")
+    if n >= 2 ** 31:
+        raise ValueError(f"{n} rows: need fewer than 2^31")
+    lib = _lib.load()
+    count = np.zeros(1, dtype=np.int64)
+    if _is_dev(c):
+        import torch
+
+        if stride != nb:
+            c = c.contiguous()  # type: ignore[attr-defined]
+        dev = c.device  # type: ignore[attr-defined]
+        out_t = torch.empty((2, n), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.bbh_jt_components(_lib.ptr(c), n, nb, radius, int(out_t[0].data_ptr()) if return_roots and n else None,
+                                         int(out_t[1].data_ptr()) if n else None, count.ctypes.data, st))
+        return (out_t[1], int(count[0]), out_t[0]) if return_roots else (out_t[1], int(count[0]))
+    out = np.empty((2, n), dtype=np.int32)
+    _lib.check(lib.bbh_jt_components(c.ctypes.data, n, nb, radius, out[0].ctypes.data if return_roots and n else None,  # type: ignore[attr-defined]
+                                     out[1].ctypes.data if n else None, count.ctypes.data, None))
+    labels = out[1].astype(np.int64)
+    return (labels, int(count[0]), out[0].astype(np.int64)) if return_roots else (labels, int(count[0]))
 
 
 def jt_sim_matrix_packed(arr: NDArray[np.uint8]) -> NDArray[np.float64]:

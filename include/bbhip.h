@@ -135,6 +135,22 @@ int bbh_jt_radius(const uint8_t* queries, int64_t nq, int64_t q_stride, const ui
                   double radius, const int32_t* exclude, int64_t capacity, int64_t* out_offsets, int64_t* out_total,
                   int32_t* out_idx, uint32_t* out_inter, uint32_t* out_union, void* stream);
 
+/* The connected components of a table at a Jaccard distance, without storing an edge: what a union-find over the CSR of
+ * bbh_jt_radius(rows, rows, radius) would give.  Rows a and b are linked iff that call reports the pair: d <= radius in
+ * float64, d = (u - i) / u as one division, 0.0 where u == 0; a pair at the radius bit for bit is linked, one ulp above is
+ * not.  Components are the transitive closure: radius < 0 gives n of them, radius >= 1 one, radius = 0 groups identical rows
+ * (and the all-zero rows with each other).  rows: n x nbytes, contiguous; 0 <= n < 2^31.
+ * out_root: n int32, the smallest row index of the row's component.  out_label: n int32, the rank of that root among the
+ * roots in ascending order, 0 .. count - 1 (scipy.sparse.csgraph.connected_components' labelling).  *out_count: the number
+ * of components.  Each output is optional, one at least is needed.  n == 0 is BBH_OK and writes *out_count = 0 only.
+ * BBH_ERR_INVALID, with nothing written: a NaN radius, n < 0, n >= 2^31, nbytes <= 0, all three outputs null.  Every
+ * pointer may be host or device memory.  The call synchronises the stream.  Device memory beside the operands: 4 bytes per
+ * row of popcounts, 4 of forest, 4 more where out_root is null or on the host.  The result is a function of the rows and the
+ * radius alone: it does not depend on the kernel that served the call, on how the grid was split or on the order in which
+ * workgroups ran. */
+int bbh_jt_components(const uint8_t* rows, int64_t n, int64_t nbytes, double radius, int32_t* out_root,
+                      int32_t* out_label, int64_t* out_count, void* stream);
+
 /* Test hook: one v_mfma_i32_16x16x64_i8 with the operand lane maps bb_assign.hip documents.
  * a: 16 x 64 int8, b: 64 x 16 int8, d: 16 x 16 int32 = a @ b, all row-major, host or device. */
 int bbh_mfma_i8_probe(const int8_t* a, const int8_t* b, int32_t* d, void* stream);
