@@ -396,11 +396,13 @@ def expand(snap):
 
 
 def replay(c, ops):
-    r"""tree_abi_cases.replay, compact, with snap["edge"] = OracleEngine.edge_counts()."""
+    r"""tree_abi_cases.replay, compact, with snap["edge"] = OracleEngine.edge_counts() and snap["walk"] = the pre-order walk
+    without its linear sums (test_edge_reference.py holds it against the reference's tree, internal nodes included)."""
     eng = T.make_oracle(c)
     snap = T.run(eng, ops)
     snap["edge"] = eng.edge_counts()
     snap["tie_depths"] = eng.tie_depths()
+    snap["walk"] = eng.walk(ls=False)
     eng.close()
     return compact(snap)
 
