@@ -23,6 +23,7 @@ BBH_ERR_NO_DEVICE = 3
 BBH_ERR_CAPACITY = 4
 BBH_ERR_STATE = 5
 BBH_TOPK_MAX = 64  # include/bbhip.h
+BBH_LEADERS_TIES_HIGH = 1  # include/bbhip.h
 
 _vp = C.c_void_p
 _i32 = C.c_int32
@@ -44,6 +45,7 @@ _PROTOTYPES = {
     "bbh_jt_topk": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "bbh_jt_radius": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _f64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbh_jt_components": (_int, [_vp, _i64, _i64, _f64, _vp, _vp, _vp, _vp]),
+    "bbh_jt_leaders": (_int, [_vp, _i64, _i64, _f64, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp]),
     "bbh_mfma_i8_probe": (_int, [_vp, _vp, _vp, _vp]),
     "bbh_unpack": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "bbh_pack": (_int, [_vp, _i64, _i64, _vp, _vp]),

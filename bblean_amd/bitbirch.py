@@ -648,6 +648,38 @@ class BitBirch:
         self._n_global_clusters = count
         return self
 
+    def centroid_leaders(self, radius: float | None = None, sort: bool = True, weighted: bool = True) -> tuple[NDArray[np.int64], int, NDArray[np.int64]]:
+        r"""Leader clustering (sphere exclusion, Taylor-Butina) of the centroids at Jaccard distance `radius` (default
+        ``1 - threshold``): ``(labels int64 (K,), n_clusters, centres int64 (K,))`` over the positions of
+        `get_centroids(sort=sort)`.  Two centroids are neighbours iff `centroid_radius_neighbors(radius)` lists one for the
+        other.  The centroid with the most around it becomes a centre and takes its neighbours, then the best of the rest,
+        and so on (`similarity.jt_leaders_packed`): every member is within `radius` of its centre, no two centres are within
+        `radius` of each other.  With `weighted` every cluster counts with its number of molecules, so "the most around it"
+        counts molecules, not centroids.  ``centres[p]`` is the position of ``p``'s centre, ``labels[p]`` the rank of that
+        centre among the centres in ascending position.  Computed on the device without the graph.  The model is left as
+        it is."""
+        from bblean_amd import similarity
+
+        radius = similarity._radius_check(1.0 - self.threshold if radius is None else radius)
+        order = self._leaf_order(sort)
+        weights = np.asarray(self._leaves()["n"], dtype=np.int64)[order] if weighted else None
+        gather = getattr(self._engine, "gather_centroids", None)
+        cents = gather(order, device_out=True) if gather is not None else np.ascontiguousarray(self._leaves()["cents"][order])
+        labels, count, centres = similarity.jt_leaders_packed(cents, radius, weights=weights, return_centres=True)
+        if hasattr(labels, "cpu"):
+            labels, centres = labels.cpu().numpy(), centres.cpu().numpy()
+        return np.asarray(labels, dtype=np.int64), int(count), np.asarray(centres, dtype=np.int64)
+
+    def lead_clusters(self, radius: float | None = None, weighted: bool = True) -> "BitBirch":
+        r"""Merge every cluster into the cluster of its leader at Jaccard distance `radius` (default ``1 - threshold``):
+        `centroid_leaders`.  Unlike `link_clusters` a merged cluster has a centre and a radius: all of its centroids are
+        within `radius` of the centre's.  Stores the labels where `global_clustering` stores its own (1-based, in
+        ``sort=True`` order), so every ``global_clusters=True`` getter and `save` / `load` see the merged clusters."""
+        labels, count, _ = self.centroid_leaders(radius, sort=True, weighted=weighted)
+        self._global_clustering_centroid_labels = labels + 1
+        self._n_global_clusters = count
+        return self
+
     def route(self, X, input_is_packed: bool = True, n_features: int | None = None, sort: bool = True):  # type: ignore[no-untyped-def]
         r"""Route fingerprints through the fitted tree WITHOUT inserting them: ``(cluster, accept, sim)``, one entry per row.
 

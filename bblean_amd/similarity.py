@@ -46,6 +46,7 @@ __all__ = [
     "jt_topk_packed",
     "jt_radius_packed",
     "jt_components_packed",
+    "jt_leaders_packed",
     "jt_compl_isim_segments",
     "jt_cluster_stats_segments",
 ]
@@ -501,6 +502,106 @@ def jt_components_packed(rows: object, radius: float, return_roots: bool = False
                                      out[1].ctypes.data if n else None, count.ctypes.data, None))
     labels = out[1].astype(np.int64)
     return (labels, int(count[0]), out[0].astype(np.int64)) if return_roots else (labels, int(count[0]))
+
+
+def _leaders_weights(weights: object, n: int) -> object:
+    r"""Weights of `jt_leaders_packed`, checked before the library is called: ``n`` integers in ``[0, 2^32)``.  Host values
+    come back as a contiguous uint32 array; a device tensor (int32 or int64, one reduction checks the range) as the int32
+    tensor that holds the same 32 bits."""
+    if _is_dev(weights):
+        import torch
+
+        if weights.dim() != 1 or int(weights.shape[0]) != n:  # type: ignore[attr-defined]
+            raise ValueError(f"weights must hold one integer per row ({n})")
+        if weights.dtype not in (torch.int32, torch.int64):  # type: ignore[attr-defined]
+            raise TypeError(f"weights on the device must be int32 or int64, got {weights.dtype}")  # type: ignore[attr-defined]
+        if n:
+            lo, hi = (int(v) for v in torch.aminmax(weights))  # type: ignore[call-overload]
+            if lo < 0 or hi >= 2 ** 32:
+                raise ValueError("weights must lie in [0, 2^32)")
+        if weights.dtype == torch.int64:  # type: ignore[attr-defined]
+            weights = weights.contiguous().view(torch.int32)[::2]  # type: ignore[attr-defined]  # (the low words: little endian)
+        return weights.contiguous()  # type: ignore[attr-defined]
+    arr = np.asarray(weights)
+    if arr.ndim != 1 or arr.shape[0] != n:
+        raise ValueError(f"weights must hold one integer per row ({n})")
+    if arr.dtype.kind not in "iu":
+        raise TypeError(f"weights must be integers, got {arr.dtype}")
+    if n and (int(arr.min()) < 0 or int(arr.max()) >= 2 ** 32):
+        raise ValueError("weights must lie in [0, 2^32)")
+    return np.ascontiguousarray(arr.astype(np.uint32))
+
+
+def jt_leaders_packed(rows: object, radius: float, weights: object = None, ties: str = "low", return_centres: bool = False,  # type: ignore[no-untyped-def]
+                      return_density: bool = False):
+    r"""Leader clustering (sphere exclusion, Taylor-Butina) of a packed table at Jaccard distance ``radius``:
+    ``(labels, n_clusters[, centres][, density])``.  Rows ``a != b`` are neighbours iff ``jt_radius_packed(rows, rows,
+    radius)`` reports the pair (``(u - i) / u <= radius`` as one float64 division, 0.0 where ``u == 0``; a pair at
+    ``radius`` bit for bit is a neighbour pair).  ``density[a]`` is ``weights[a]`` plus the weights of ``a``'s neighbours
+    (all 1 without ``weights``), exact.  The rows are walked in priority order - the higher density first, among equal
+    densities the lower row first (``ties="high"``: the higher row) - and a row that is not yet taken becomes a centre
+    and takes all of its neighbours that are not yet taken; densities are never recomputed.  So every member is within
+    ``radius`` of its centre and no two centres are within ``radius`` of each other - without the graph: no edge is stored.
+
+    ``labels[v]`` is the rank of ``v``'s centre among the centres in ascending row index (`jt_components_packed`'s rule);
+    ``centres[v]`` is the row index of ``v``'s centre, a centre names itself.  The order in which the sequential procedure
+    creates the clusters is the centres sorted by ``(-density, row)`` (``ties="high"``: ``(-density, -row)``).
+    ``radius = 0`` groups duplicates, ``radius < 0`` leaves every row alone, ``radius >= 1`` gives one cluster.
+
+    ``weights``: optional, one integer in ``[0, 2^32)`` per row; 0 is allowed.  NumPy rows -> int64 NumPy labels and
+    centres, uint64 density; a device tensor -> int32 device labels and centres, int64 device density, on the current
+    stream (the call synchronises it).  Device weights are int32 or int64."""
+    radius = _radius_check(radius)
+    if ties not in ("low", "high"):
+        raise ValueError(f'ties must be "low" or "high", got {ties!r}')
+    if not _is_dev(rows):
+        arr = np.asarray(rows)
+        if arr.ndim == 2 and arr.dtype != np.uint8:
+            raise TypeError(f"rows must be packed uint8, got {arr.dtype}")
+    elif str(rows.dtype) != "torch.uint8":  # type: ignore[attr-defined]
+        raise TypeError(f"rows must be packed uint8, got {rows.dtype}")  # type: ignore[attr-defined]
+    c, n, nb, stride = _u8_2d(rows, "rows")
+    if nb < 1:
+        raise RuntimeError("rows must have at least one byte per row")
+    if n >= 2 ** 31:
+        raise ValueError(f"{n} rows: need fewer than 2^31")
+    if weights is not None:
+        weights = _leaders_weights(weights, n)
+    flags = _lib.BBH_LEADERS_TIES_HIGH if ties == "high" else 0
+    lib = _lib.load()
+    count = np.zeros(1, dtype=np.int64)
+    if _is_dev(c):
+        import torch
+
+        if stride != nb:
+            c = c.contiguous()  # type: ignore[attr-defined]
+        dev = c.device  # type: ignore[attr-defined]
+        if weights is not None and not _is_dev(weights):
+            weights = torch.from_numpy(weights.view(np.int32)).to(dev)
+        out_t = torch.empty((2, n), dtype=torch.int32, device=dev)
+        dens_t = torch.empty(n, dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.bbh_jt_leaders(_lib.ptr(c), n, nb, radius, _lib.ptr(weights) if n else None, flags,
+                                      int(out_t[0].data_ptr()) if return_centres and n else None,
+                                      int(out_t[1].data_ptr()) if n else None, count.ctypes.data,
+                                      int(dens_t.data_ptr()) if return_density and n else None, st))
+        res: tuple = (out_t[1], int(count[0]))
+        if return_centres:
+            res += (out_t[0],)
+        if return_density:
+            res += (dens_t,)
+        return res
+    out = np.empty((2, n), dtype=np.int32)
+    dens = np.empty(n, dtype=np.uint64)
+    _lib.check(lib.bbh_jt_leaders(c.ctypes.data, n, nb, radius, _lib.ptr(weights) if n else None, flags,  # type: ignore[attr-defined]
+                                  out[0].ctypes.data if return_centres and n else None, out[1].ctypes.data if n else None,
+                                  count.ctypes.data, dens.ctypes.data if return_density and n else None, None))
+    res = (out[1].astype(np.int64), int(count[0]))
+    if return_centres:
+        res += (out[0].astype(np.int64),)
+    if return_density:
+        res += (dens,)
+    return res
 
 
 def jt_sim_matrix_packed(arr: NDArray[np.uint8]) -> NDArray[np.float64]:

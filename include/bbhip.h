@@ -151,6 +151,35 @@ int bbh_jt_radius(const uint8_t* queries, int64_t nq, int64_t q_stride, const ui
 int bbh_jt_components(const uint8_t* rows, int64_t n, int64_t nbytes, double radius, int32_t* out_root,
                       int32_t* out_label, int64_t* out_count, void* stream);
 
+/* Leader clustering (sphere exclusion, Taylor-Butina) of a table at a Jaccard distance, without storing an edge.  Rows
+ * a != b are neighbours iff bbh_jt_radius(rows, rows, radius) reports the pair: d <= radius in float64, d = (u - i) / u as
+ * one division, 0.0 where u == 0; a pair at the radius bit for bit is a neighbour pair, one ulp above is not.
+ * density[a] = w[a] + the sum of w[b] over a's neighbours, exact in uint64; w is 1 everywhere where weights is null.
+ * Priority: the higher density first; among equal densities the lower row index first, with BBH_LEADERS_TIES_HIGH the higher
+ * row index.  The result is what this sequential procedure gives: walk the rows in priority order; a row not yet taken
+ * becomes a centre and takes all of its neighbours that are not yet taken; a row already taken is skipped; densities are
+ * never recomputed.  Equivalently: the centres are the lexicographically first maximal independent set of the neighbour
+ * graph under the priority order (a row is a centre iff none of its higher-priority neighbours is one) and every other
+ * row belongs to its highest-priority neighbouring centre.  So every member is within radius of its centre and no two
+ * centres are within radius of each other.  radius < 0: every row is its own centre, density = w.  radius >= 1: one
+ * cluster around the first row in priority order.  -0.0 is 0: identical rows group, and the all-zero rows with each other.
+ * rows: n x nbytes, contiguous, any alignment; 0 <= n < 2^31.  weights: optional, n uint32, 0 allowed.
+ * out_centre: n int32, the row index of the row's centre (a centre names itself).  out_label: n int32, the rank of that
+ * centre among the centres in ascending row index, 0 .. count - 1 (bbh_jt_components' rule).  *out_count: the number of
+ * clusters.  out_density: n uint64.  Each output is optional, one at least is needed.  n == 0 is BBH_OK and writes
+ * *out_count = 0 only.  BBH_ERR_INVALID, with nothing written: a NaN radius, n < 0, n >= 2^31, nbytes <= 0, null rows with
+ * n > 0, all four outputs null, a flag bit other than bit 0.  Every pointer may be host or device memory.  The call
+ * synchronises the stream.  Device memory beside the operands: per row 4 bytes of popcounts and 4 of marks (later the
+ * ranks), 8 of densities where out_density is null or on the host, 4 of centres where out_centre is null or on the host;
+ * per row that has a neighbour 32 bytes of index maps, state and lists and a copy of the row, rows of up to 256 bytes
+ * zero-padded to 8, 16, 32, 64, 128 or 256 bytes.  Host memory: 12 bytes per row while the rows are ranked.  The result is
+ * a function of rows, radius, weights and flags alone: it does not depend on the kernel that served the width, on how the
+ * grid was split, on the order in which workgroups ran or on BBHIP_LEADERS_ROUNDS (after how many rounds the sequential
+ * tail starts). */
+#define BBH_LEADERS_TIES_HIGH 1u
+int bbh_jt_leaders(const uint8_t* rows, int64_t n, int64_t nbytes, double radius, const uint32_t* weights, uint32_t flags,
+                   int32_t* out_centre, int32_t* out_label, int64_t* out_count, uint64_t* out_density, void* stream);
+
 /* Test hook: one v_mfma_i32_16x16x64_i8 with the operand lane maps bb_assign.hip documents.
  * a: 16 x 64 int8, b: 64 x 16 int8, d: 16 x 16 int32 = a @ b, all row-major, host or device. */
 int bbh_mfma_i8_probe(const int8_t* a, const int8_t* b, int32_t* d, void* stream);
